@@ -20,6 +20,16 @@ TFLOP/s = 2 m n k / time (8 m n k complex; test_double.cu:440).
 ranks (one process per GPU, RCCL) before touching the GPU.  --partition rows selects the weak-scaling
 row-block partition instead (rank r: the 8192-row block r of an (8192 N) x 8192 x 8192 product).
 
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, the roofline
+figures that come from the timed steps' own phase timers).  --full adds every phase that takes runs of its own after
+the timed region: accuracy against the double-double GEMM, the MFMA ceiling, the power sample, rocBLAS DGEMM, cfg3's
+shape on one GPU, the CPU baseline, and for sharded runs the single-GPU baseline and the other partitions (each can
+be switched off again with its --no-* option).
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (C on one GPU,
+C_rank<r> for each rank of a multi-GPU run; float64, a complex array with a trailing (re, im) axis).  An output
+larger than the dump budget is sampled at flat indices drawn from a fixed seed, the same in every run.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -71,6 +81,12 @@ def parse(argv=None):
     ap.add_argument("--order", choices=["moduli", "columns"], default="moduli",
                     help="moduli partition: unit order of gemmul8.dist.ShardPlan")
     ap.add_argument("--gather", action="store_true", help="moduli partition: collect C on rank 0 in the step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the accuracy check, the MFMA ceiling, the power sample, rocBLAS "
+                         "DGEMM, cfg3's shape on one GPU, the CPU baseline and (sharded runs) the single-GPU baseline and "
+                         "the other partitions; the --no-* options below switch single ones off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; a seeded sample when large)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-accuracy", action="store_true")
     ap.add_argument("--no-dgemm", action="store_true")
@@ -83,6 +99,49 @@ def parse(argv=None):
     ap.add_argument("--no-single-gpu", action="store_true",
                     help="sharded runs: skip timing the same call on one GPU after the timed region")
     return ap.parse_args(argv)
+
+
+OPTIONAL_PHASES = ("no_cpu_baseline", "no_accuracy", "no_dgemm", "no_cfg3_1gpu", "no_power", "no_variants",
+                   "no_single_gpu", "no_ceiling")
+
+
+def select_phases(args):
+    """the phases after the timed region belong to --full: a plain run switches every one of them off"""
+    args.no_ceiling = False
+    if not args.full:
+        for name in OPTIONAL_PHASES:
+            setattr(args, name, True)
+    return args
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # of array data per run, all ranks together
+DUMP_SEED = 20240613
+
+
+def dump_outputs(path, outputs, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the tensors of `outputs` ({name: tensor or None}) as path/<name>.npy, float32 or float64 (a
+    complex tensor with a trailing (re, im) axis).  Within the budget the arrays keep their shape; beyond it each is
+    flattened and sampled at sorted flat indices drawn from DUMP_SEED (with replacement), its share of the budget in
+    proportion to its size -- the same indices in every run with the same shapes.  Returns {name: elements written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    outputs = {name: t for name, t in outputs.items() if t is not None}
+    total = sum(t.numel() * t.element_size() for t in outputs.values())
+    written = {}
+    for name, t in outputs.items():
+        if total > budget:
+            flat = t.reshape(-1)
+            keep = max(1, flat.numel() * budget // total)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=keep))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+        if t.is_complex():
+            t = torch.view_as_real(t.contiguous())
+        elif t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        a = t.detach().cpu().contiguous().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 # The line's dicts (extra, its variants, roofline) change after the timed region while the watchdog thread
@@ -563,7 +622,7 @@ def composite_roofline(work, ms_per_step, phase_ms=None, world=1):
 
 
 def main():
-    args = parse()
+    args = select_phases(parse())
     maybe_launch(args)
     world, rank, backend = dist_setup()
     import gemmul8 as G
@@ -641,8 +700,9 @@ def main():
     e_start, e_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e_start.record()
+    last = None
     for _ in range(args.steps):
-        step(trace)
+        last = step(trace)
     e_end.record()
     barrier(world)
     wall = time.perf_counter() - t0
@@ -653,8 +713,14 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     # strong scaling (one product over all ranks) or weak (row partition: one product per rank)
     value = flop_per * (1 if (sharded or world == 1) else world) * args.steps / dt / 1e12
+    if args.dump_outputs:
+        # what the last timed step handed to its caller, before any later phase calls the step again
+        arm("dump outputs")
+        dump_outputs(args.dump_outputs, {"C" if world == 1 else f"C_rank{rank}": last}, DUMP_BUDGET_BYTES // world)
+        barrier(world)
+    del last
 
-    avg = [x / args.steps for x in phase_ms]
+    avg =[x / args.steps for x in phase_ms]
     extra = {}
     # int8 MACs per output element and modulus relative to m n k: 1 real, 4 complex big matrix, 3 Karatsuba
     fmac = (3.0 if L["nsub"] == 3 else 4.0) if cplx else 1.0
@@ -706,6 +772,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "ms_per_step_wall": round(wall / args.steps * 1e3, 4),
             "timing": "HIP events on the stream over the K steps, max over ranks (ms_per_step_wall: host clock of the "
@@ -827,7 +894,7 @@ def main():
         # measured live after the timed region: the same MFMA alone on uniformly random operand bytes
         # (the residue distribution) in registers -- the clock the chip holds under that load bounds
         # any int8 GEMM on such data
-        ceiling = G.mfma_ceiling()
+        ceiling = 0.0 if args.no_ceiling else G.mfma_ceiling()
         if ceiling > 0:
             put(roofline, "data_bound_ceiling", round(ceiling, 1))
             put(roofline, "frac_of_data_bound_ceiling", round(achieved / ceiling, 4))

@@ -107,6 +107,47 @@ def test_new_bench_options():
     assert b.parse([]).order == "moduli" and not b.parse([]).no_single_gpu
 
 
+def test_plain_run_switches_every_optional_phase_off(monkeypatch):
+    """a plain run measures the headline only; --full runs every phase after the timed region, minus its --no-*"""
+    b = _bench()
+    plain = b.select_phases(b.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"]))
+    assert not plain.full and plain.dump_outputs is None and (plain.steps, plain.warmup) == (5, 2)
+    assert all(getattr(plain, name) for name in b.OPTIONAL_PHASES)
+    full = b.select_phases(b.parse(["--full"]))
+    assert full.full and not any(getattr(full, name) for name in b.OPTIONAL_PHASES)
+    some = b.select_phases(b.parse(["--full", "--no-power", "--no-cpu-baseline"]))
+    assert [name for name in b.OPTIONAL_PHASES if getattr(some, name)] == ["no_cpu_baseline", "no_power"]
+    # the ranks of a --gpus N run are started with the same options
+    argv = ["--gpus", "8", "--full", "--dump-outputs", "d"]
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    assert b.launch_command(b.parse(argv), argv)[-len(argv):] == argv
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: float64 .npy files; within the budget the array as it is, beyond it the same seeded flat
+    sample in every run, the budget shared in proportion; complex as (re, im); None (a rank without output) skipped"""
+    import numpy as np
+    import torch
+    b = _bench()
+    C = torch.arange(6 * 5, dtype=torch.float64).reshape(6, 5).t()  # a strided view, as the row partition returns
+    Z = torch.complex(torch.arange(4.0, dtype=torch.float64), -torch.arange(4.0, dtype=torch.float64))
+    n = b.dump_outputs(str(tmp_path / "a"), {"C": C, "Z": Z, "none": None})
+    assert n == {"C": 30, "Z": 8} and sorted(os.listdir(tmp_path / "a")) == ["C.npy", "Z.npy"]
+    got = np.load(tmp_path / "a" / "C.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, C.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "Z.npy"), np.stack([np.arange(4.0), -np.arange(4.0)], 1))
+    # beyond the budget: sorted flat indices from the fixed seed, the same in a second run and for a second build
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    for d in ("b", "c"):
+        assert b.dump_outputs(str(tmp_path / d), {"C": big, "D": big.double()}, budget=1200) == {"C": 100, "D": 100}
+    s1, s2 = np.load(tmp_path / "b" / "C.npy"), np.load(tmp_path / "c" / "C.npy")
+    assert s1.dtype == np.float32 and s1.nbytes + np.load(tmp_path / "b" / "D.npy").nbytes <= 1200
+    assert np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0) and len(set(s1.tolist())) > 50
+    idx = np.sort(np.random.default_rng(b.DUMP_SEED).integers(0, 1000, size=100))
+    assert np.array_equal(s1, idx.astype(np.float32))  # big[i] == i: the values name the sampled positions
+    assert b.DUMP_BUDGET_BYTES <= 32 << 20
+
+
 def test_physical_core_count_from_cpuinfo(monkeypatch, tmp_path):
     """cpu_baseline's all-core bound counts distinct (physical id, core id) pairs, not SMT siblings"""
     b = _bench()

@@ -24,17 +24,17 @@ for step in "$@"; do
       timeout -k 10 120 python tests/golden/make_golden_cfg1.py $OUT/golden_cfg1 > $OUT/golden_cfg1.log 2>&1
       rc=$?; tail -2 $OUT/golden_cfg1.log ;;
     bench)
-      timeout -k 10 600 python bench.py $arg > $OUT/bench_$i.json 2> $OUT/bench_$i.err
+      timeout -k 10 600 python bench.py --full $arg > $OUT/bench_$i.json 2> $OUT/bench_$i.err
       rc=$?; cat $OUT/bench_$i.json ;;
     gloo2)
-      GEMMUL8_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 $arg > $OUT/gloo2_$i.json 2> $OUT/gloo2_$i.err
+      GEMMUL8_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --full $arg > $OUT/gloo2_$i.json 2> $OUT/gloo2_$i.err
       rc=$?; cat $OUT/gloo2_$i.json ;;
     gloo4)
-      GEMMUL8_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 4 $arg > $OUT/gloo4_$i.json 2> $OUT/gloo4_$i.err
+      GEMMUL8_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 4 --full $arg > $OUT/gloo4_$i.json 2> $OUT/gloo4_$i.err
       rc=$?; cat $OUT/gloo4_$i.json ;;
     gloo8)
       # the driver's 8-rank bench rehearsed on one GPU (gloo, ranks sharing the device; timing meaningless)
-      GEMMUL8_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --gpus 8 $arg > $OUT/gloo8_$i.json 2> $OUT/gloo8_$i.err
+      GEMMUL8_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --gpus 8 --full $arg > $OUT/gloo8_$i.json 2> $OUT/gloo8_$i.err
       rc=$?; cat $OUT/gloo8_$i.json ;;
     profile)
       timeout -k 10 900 bash tools/profile.sh $arg > $OUT/profile_$i.log 2>&1

@@ -16,7 +16,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 # --no-cfg3-1gpu, --no-power: the N = 1 line's extra timing of cfg3's 16384^3 shape and its one-second power loop
 # (after the timed region) would mix a second shape and ~160 extra launches into the per-kernel averages
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python3 bench.py --no-cfg3-1gpu --no-power $BENCH_ARGS \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python3 bench.py --full --no-cfg3-1gpu --no-power $BENCH_ARGS \
   > $OUT/bench.json 2> $OUT/trace.log
 PMC_ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-accuracy --no-dgemm --no-cfg3-1gpu --no-power $BENCH_ARGS"
 i=0

@@ -62,6 +62,25 @@ int gemmul8_gemm_lowmem(void *stream, int op_a, int op_b, size_t m, size_t n, si
                         const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode, void *work,
                         int compute_type, unsigned slice_planes, double *phase_ns);
 
+/* --- strided-batched call ----------------------------------------------------------------------
+ * gemmul8_gemm applied to each b in [0, batch) with A + b * stride_a, B + b * stride_b, C + b * stride_c
+ * (strides in elements; stride_a or stride_b may be 0: one operand shared by the batch); alpha and beta are one
+ * host value for the batch.  Every element's result is bit-identical to gemmul8_gemm on that element.
+ * Real f64 operands in fast mode with round_up(k, 64) <= 2048 run ONE split, ONE product and ONE CRT launch for
+ * the whole batch (the product kernel reported as "gemm_i8_batched_kernel" / "gemm_i8_batched_onetile_kernel");
+ * every other form runs the single-problem phases element by element in the same workspace.
+ * The workspace size is for the whole batch and grows linearly with it; callers short of memory split the batch.
+ * stride_c < ldc * n with batch > 1 returns GEMMUL8_E_SIZE; gemmul8_gemm's argument checks apply unchanged;
+ * batch == 0 returns GEMMUL8_OK; on any error nothing is enqueued.  phase_ns as gemmul8_gemm (the fallback loop
+ * sums its elements' phase times). */
+size_t gemmul8_work_size_strided_batched(size_t m, size_t n, size_t k, unsigned num_moduli, int compute_type,
+                                         size_t batch);
+int gemmul8_gemm_strided_batched(void *stream, int op_a, int op_b, size_t m, size_t n, size_t k, int type_a,
+                                 int type_b, int type_c, const void *alpha, const void *A, size_t lda,
+                                 size_t stride_a, const void *B, size_t ldb, size_t stride_b, const void *beta, void *C,
+                                 size_t ldc, size_t stride_c, size_t batch, unsigned num_moduli, int fastmode,
+                                 void *work, int compute_type, double *phase_ns);
+
 /* --- phase entry points (multi-GPU sharding, gemmul8/dist.py) ------------------------------------
  * gemmul8_gemm == gemmul8_split(0, N) + gemmul8_products(0, N) + gemmul8_recombine, on one stream.
  * Splitting the moduli range lets a rank produce only the residue planes [mod_begin, mod_end)

@@ -579,10 +579,154 @@ static int prepare(void *stream, int op_a, int op_b, size_t m, size_t n, size_t 
     return GEMMUL8_OK;
 }
 
+// ---------------- strided-batched call ----------------
+// Workspace of a batch: one problem's regions (make_layout, real), the per-element ones repeated `batch` times.
+// Slice and residue planes are [batch][N] with the per-problem strides, so plane pair q = b N + j; the shifts
+// are [batch][m_pad] / [batch][n_pad]; the bound / sft0 areas (unused by the hot path) and the tile-queue area
+// exist once.  total(batch) = L.total + (batch - 1) * per_elem: a single problem's layout always fits, which
+// is what the host-loop fallback runs in.
+struct BatchLayout {
+    Layout L;
+    size_t offA, offB, offR, offSftA, offSftB, offQueue, per_elem, total;
+};
+static BatchLayout make_batch_layout(size_t m, size_t n, size_t k, unsigned N, size_t batch) {
+    BatchLayout B{};
+    B.L = make_layout(m, n, k, N, false);
+    const Layout &L = B.L;
+    const size_t rA = round_up(L.planeA * N, 256), rB = round_up(L.planeB * N, 256), rR = round_up(L.planeR * N, 256);
+    const size_t rSA = round_up(L.m_pad * 2, 256), rSB = round_up(L.n_pad * 2, 256);
+    B.per_elem = rA + rB + rR + rSA + rSB;
+    const size_t nb = batch ? batch : 1;
+    size_t off = 0;
+    B.offA = off; off += rA * nb;
+    B.offB = off; off += rB * nb;
+    B.offR = off; off += rR * nb;
+    B.offSftA = off; off += rSA * nb;
+    B.offSftB = off; off += rSB * nb;
+    B.offQueue = off;
+    B.total = L.total + (nb - 1) * B.per_elem;
+    return B;
+}
+
+// the hot path: real f64, fast mode, round_up(k, 64) <= 2048 -- split, products and CRT once each for the batch
+static bool batched_hot(const Call &c, size_t batch) {
+    return c.fast && !c.cplx && c.A.dbl && c.B.dbl && c.ot == OutType::F64 && c.VT == 128 && c.k > 0 &&
+           round_up(c.k, KSTEP) <= 2048 && batch <= 65535;
+}
+
+// returns GEMMUL8_OK / GEMMUL8_E_HIP, or 1 when the hot path does not apply and nothing was enqueued
+static int run_batched(const Call &c, size_t strideA, size_t strideB, size_t strideC, size_t batch, double *phase_ns) {
+    const BatchLayout B = make_batch_layout(c.m, c.n, c.k, c.N, batch);
+    const Layout &L = B.L;
+    int8_t *base = static_cast<int8_t *>(c.work);
+    int8_t *A8 = base + B.offA, *B8 = base + B.offB;
+    uint8_t *R = reinterpret_cast<uint8_t *>(base + B.offR);
+    int16_t *sftA = reinterpret_cast<int16_t *>(base + B.offSftA), *sftB = reinterpret_cast<int16_t *>(base + B.offSftB);
+    uint32_t *queue = reinterpret_cast<uint32_t *>(base + B.offQueue);
+    const bool shareA = batch > 1 && strideA == 0, shareB = batch > 1 && strideB == 0;
+
+    const bool capturing = is_capturing(c.st);
+    if (phase_ns && capturing)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    const bool want_events = phase_ns != nullptr && !capturing;
+    bool record;
+    timing::Rec rec{};
+    {
+        std::lock_guard<std::mutex> g(timing::mu);
+        record = want_events || (timing::enabled && !capturing);
+        if (record) rec = timing::acquire();
+    }
+    auto give_back = [&]() {
+        if (record) {
+            std::lock_guard<std::mutex> g(timing::mu);
+            timing::pool.push_back(rec);
+        }
+    };
+    ModParams MP = make_mod_params(c.N);
+    MP.zero_queue = queue;
+    {
+        timing::Phase split(record, c.st, rec.start, nullptr);
+        if (!split_fused_batched(c.A, c.m, strideA, c.B, c.n, strideB, c.k, batch, c.VT, oz2_log2M_fast[c.N - 2], sftA,
+                                 sftB, A8, B8, L, MP, c.st)) {
+            give_back();
+            return 1;
+        }
+        split.end();
+    }
+    if (!launch_ok()) return give_back(), GEMMUL8_E_HIP;
+    {
+        timing::Phase prod(record, c.st, rec.prod0, rec.prod1);
+        if (!gemm_i8_batched(A8, B8, L, c.N, batch, shareA, shareB, R, MP, c.st, queue, true)) g_launch_failed = true;
+        prod.end();
+    }
+    if (!launch_ok()) return give_back(), GEMMUL8_E_HIP;
+    {
+        timing::Phase crt(record, c.st, nullptr, rec.crt1);
+        crt_inverse_batched(R, L, batch, c.N * L.planeR, sftA, shareA ? 0 : L.m_pad, sftB, shareB ? 0 : L.n_pad,
+                            make_crt_params(c.N, false), c.alpha, c.beta, c.C, c.ldc, strideC, c.st,
+                            g_epilogue_mode.load(std::memory_order_relaxed));
+        crt.end();
+    }
+    if (!launch_ok()) return give_back(), GEMMUL8_E_HIP;
+    if (want_events) {
+        float t[4];
+        timing::read(rec, t);
+        for (int i = 0; i < 4; ++i) phase_ns[i] = t[i] * 1e6;
+    }
+    if (record) {
+        std::lock_guard<std::mutex> g(timing::mu);
+        if (timing::enabled) timing::pending.push_back(rec);
+        else timing::pool.push_back(rec);
+    }
+    return GEMMUL8_OK;
+}
+
 }  // namespace oz2
 
 // =============================== C ABI ===================================
 extern "C" {
+
+size_t gemmul8_work_size_strided_batched(size_t m, size_t n, size_t k, unsigned num_moduli, int compute_type,
+                                         size_t batch) {
+    if (compute_type < 0 || compute_type > 3) return 0;
+    if (compute_type != GEMMUL8_REAL_DEFAULT) return oz2::make_layout(m, n, k, num_moduli, true).total;  // host loop
+    return oz2::make_batch_layout(m, n, k, num_moduli, batch).total;
+}
+
+int gemmul8_gemm_strided_batched(void *stream, int op_a, int op_b, size_t m, size_t n, size_t k, int type_a,
+                                 int type_b, int type_c, const void *alpha, const void *A, size_t lda,
+                                 size_t stride_a, const void *B, size_t ldb, size_t stride_b, const void *beta, void *C,
+                                 size_t ldc, size_t stride_c, size_t batch, unsigned num_moduli, int fastmode,
+                                 void *work, int compute_type, double *phase_ns) {
+    oz2::Call c{};
+    const int rc = oz2::prepare(stream, op_a, op_b, m, n, k, type_a, type_b, type_c, alpha, A, lda, B, ldb, beta, C,
+                                ldc, num_moduli, fastmode, work, compute_type, c);
+    if (rc != GEMMUL8_OK) return rc;
+    if (batch > 1 && stride_c < ldc * n) return GEMMUL8_E_SIZE;
+    if (phase_ns)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    if (batch == 0 || m == 0 || n == 0) return GEMMUL8_OK;
+    oz2::clear_stale_error();
+    if (oz2::batched_hot(c, batch)) {
+        const int hot = oz2::run_batched(c, stride_a, stride_b, stride_c, batch, phase_ns);
+        if (hot != 1) return hot;
+    }
+    // outside the hot path: the single-problem phases, element by element, in the same workspace
+    const size_t ea = (oz2::dt_dbl(type_a) ? 8 : 4) * (c.cplx ? 2 : 1), eb = (oz2::dt_dbl(type_b) ? 8 : 4) * (c.cplx ? 2 : 1);
+    const size_t ec = (oz2::dt_dbl(type_c) ? 8 : 4) * (c.cplx ? 2 : 1);
+    for (size_t b = 0; b < batch; ++b) {
+        oz2::Call e = c;
+        e.A.ptr = static_cast<const char *>(A) + b * stride_a * ea;
+        e.B.ptr = static_cast<const char *>(B) + b * stride_b * eb;
+        e.C = static_cast<char *>(C) + b * stride_c * ec;
+        double t[4] = {0, 0, 0, 0};
+        const int r = oz2::run(e, phase_ns ? t : nullptr);
+        if (r != GEMMUL8_OK) return r;
+        if (phase_ns)
+            for (int i = 0; i < 4; ++i) phase_ns[i] += t[i];
+    }
+    return GEMMUL8_OK;
+}
 
 size_t gemmul8_work_size(size_t m, size_t n, size_t k, unsigned num_moduli, int compute_type) {
     if (compute_type < 0 || compute_type > 3) return 0;
@@ -857,6 +1001,8 @@ const char *gemmul8_last_products_kernel(void) {
     case 3: return "gemm_i8_kernel (k-chunked)";
     case 4: return "gemm_i8_small_kernel";
     case 5: return tail ? "gemm_i8_persistent_pg_kernel+gemm_i8_small_kernel" : "gemm_i8_persistent_pg_kernel";
+    case 6: return "gemm_i8_batched_kernel";
+    case 7: return "gemm_i8_batched_onetile_kernel";
     default: return "none";
     }
 }

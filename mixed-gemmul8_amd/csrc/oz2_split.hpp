@@ -128,6 +128,13 @@ bool split_encode_pair(const OperandDesc &dA, size_t m, const OperandDesc &dB, s
 // cplx_rows: complex A bound of row v = max(bound[v], bound[v + nvec]) (scaling.hpp:2561-2588)
 void split_finalize_accurate(const int16_t *sft0, const int32_t *bound, size_t nvec, float log2M, int16_t *out,
                              hipStream_t st, bool cplx_rows = false);
+// strided-batched form of split_fused_pair: one launch whose blockIdx.y is the batch element.  Element b reads
+// A + b strideA / B + b strideB (elements) and writes its shifts at sftA + b m_pad / sftB + b n_pad and its N slice
+// planes at outA + b N planeA / outB + b N planeB; an operand with stride 0 (batch > 1) is split once, for b = 0.
+// false (nothing launched) where split_fused_pair does not apply or batch > 65535
+bool split_fused_batched(const OperandDesc &dA, size_t m, size_t strideA, const OperandDesc &dB, size_t n,
+                         size_t strideB, size_t len, size_t batch, int VT, float log2M, int16_t *sftA, int16_t *sftB,
+                         int8_t *outA, int8_t *outB, const Layout &L, const ModParams &MP, hipStream_t st);
 // p[0, n) = 0 on the stream (graph-capturable)
 void zero_i32(int32_t *p, size_t n, hipStream_t st);
 
@@ -142,9 +149,15 @@ enum class Epi : int { RESIDUE = 0, BOUND = 1, RAW = 2 };
 void gemm_i8(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned nplanes, Epi epi, void *out,
              int32_t *rowmax, int32_t *colmax, const ModParams &MP, hipStream_t st, uint32_t *queue = nullptr,
              bool queue_zeroed = false, bool tail_small = false);
+// Residue products of a batch in one launch (gemm_i8_batched_kernel / gemm_i8_batched_onetile_kernel): slice
+// planes [batch][N] ([N] for a shared operand) and residue planes R [batch][N] of the geometry L; queue as gemm_i8.
+// false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB, sub-products)
+bool gemm_i8_batched(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, size_t batch, bool shareA,
+                     bool shareB, uint8_t *R, const ModParams &MP, hipStream_t st, uint32_t *queue,
+                     bool queue_zeroed);
 // the residue-product kernel of the last RESIDUE launch: 0 none yet, 1 one-tile (gemm_i8_kernel),
 // 2 persistent (gemm_i8_persistent_kernel), 3 k-chunked one-tile launches, 4 128 x 128 (gemm_i8_small_kernel),
-// 5 persistent per-group (gemm_i8_persistent_pg_kernel); g_last_tail_small: its last planes ran as 128 x 128 tiles
+// 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit; g_last_tail_small: its last planes ran as 128 x 128 tiles
 extern std::atomic<int> g_last_residue_kernel;
 extern std::atomic<int> g_last_tail_small;
 // exhaustive exactness check of the residue epilogues (0 = biased, 1 = signed): mismatch count
@@ -155,6 +168,13 @@ enum class OutType : int { F64 = 0, F32 = 1, C64 = 2, C32 = 3 };
 // ref_epi: 1 = the reference's epilogue kernels including their non-BLAS variants (gemmul8_set_epilogue)
 void crt_inverse(const uint8_t *R, const Layout &L, const int16_t *sftA, const int16_t *sftB, const CrtParams &CP,
                  OutType ot, const void *alpha, const void *beta, void *C, size_t ldc, hipStream_t st, int ref_epi);
+
+// real f64 CRT of a batch in one launch (blockIdx.z = batch element, at most 65535): element b reads the residue
+// planes R + b strideR, the shifts sftA + b strideSA / sftB + b strideSB and writes C + b strideC (elements)
+void crt_inverse_batched(const uint8_t *R, const Layout &L, size_t batch, size_t strideR, const int16_t *sftA,
+                         size_t strideSA, const int16_t *sftB, size_t strideSB, const CrtParams &CP,
+                         const void *alpha, const void *beta, void *C, size_t ldc, size_t strideC, hipStream_t st,
+                         int ref_epi);
 
 // partial CRT sums of moduli [j0, j1) into S ([2][n][lds]: C1 then C2) and the CRT finished from summed
 // partials (real outputs; gemmul8_crt_partial / gemmul8_crt_finish)

@@ -1329,6 +1329,44 @@ __global__ __launch_bounds__(FZ_NT) void split_fused_kernel(FusedOperand a, Fuse
     }
 }
 
+// Strided-batched form (gemmul8_gemm_strided_batched): blockIdx.y is the batch element, whose operand base, shift
+// base and slice-plane base are offset before the same fused_body runs -- the reference's summation order, and
+// with it the shifts and the slices, are those of split_fused_kernel by construction.  A shared operand
+// (stride 0) is split by the blocks of element 0 only.
+struct FusedBatch {
+    size_t xa, xb;  // operand strides (elements)
+    size_t sa, sb;  // shift strides (int16)
+    size_t oa, ob;  // slice-plane strides (bytes)
+    int shareA, shareB;
+};
+template <int KMAX, bool CA, bool CB>
+__global__ __launch_bounds__(256) void split_fused_batched_kernel(FusedOperand a, FusedOperand b, FusedBatch fb,
+                                                                  size_t len, size_t ksteps, size_t kblk,
+                                                                  float log2M, ModParams MP, ModGroups G) {
+    constexpr int FZ_V = 4, FZ_NT = 256;
+    __shared__ double panel[FZ_V][FZ_ROW<KMAX>];
+    __shared__ int shl[FZ_V];
+    if (MP.zero_queue && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8) MP.zero_queue[threadIdx.x] = 0;
+    const size_t e = blockIdx.y;
+    const unsigned na = (unsigned)(a.vpad / FZ_V), nb = (unsigned)(b.vpad / FZ_V);
+    if (blockIdx.x < na) {
+        if (fb.shareA && e) return;  // block-uniform
+        a.X += e * fb.xa;
+        a.sft += e * fb.sa;
+        a.out += e * fb.oa;
+        const unsigned bx = CA ? blockIdx.x : xcd_local_block(blockIdx.x, na);
+        fused_body<KMAX, FZ_V, FZ_NT, CA, false, false, 1>(a, true, len, ksteps, kblk, log2M, MP, G, bx, panel, shl);
+    } else {
+        if (fb.shareB && e) return;
+        b.X += e * fb.xb;
+        b.sft += e * fb.sb;
+        b.out += e * fb.ob;
+        const unsigned t = blockIdx.x - na;
+        const unsigned bx = CB ? t : xcd_local_block(t, nb);
+        fused_body<KMAX, FZ_V, FZ_NT, CB, false, false, 1>(b, false, len, ksteps, kblk, log2M, MP, G, bx, panel, shl);
+    }
+}
+
 // accurate mode: sft = sft0 + floor_rd(-0.51*log2(amax) + log2M)  (int8tc::compute_sft, scaling.hpp:1504-1506)
 __global__ void finalize_accurate_sft_kernel(const int16_t *__restrict__ sft0, const int32_t *__restrict__ bound,
                                              size_t nvec, float log2M, int16_t *__restrict__ sft_out, int cplx_rows) {
@@ -1603,6 +1641,46 @@ bool split_fused_magnitudes_pair(const OperandDesc &dA, size_t m, const OperandD
                                  int16_t *sft0A, int16_t *sft0B, int8_t *outA, int8_t *outB, const Layout &L,
                                  const ModParams &MP, int32_t *bound, size_t nbound, hipStream_t st) {
     return fused_pair_launch<true>(dA, m, dB, n, len, 0.f, sft0A, sft0B, outA, outB, L, MP, bound, nbound, st);
+}
+
+bool split_fused_batched(const OperandDesc &dA, size_t m, size_t strideA, const OperandDesc &dB, size_t n,
+                         size_t strideB, size_t len, size_t batch, int VT, float log2M, int16_t *sftA, int16_t *sftB,
+                         int8_t *outA, int8_t *outB, const Layout &L, const ModParams &MP, hipStream_t st) {
+    if (VT != 128 || !fused_split_mode() || dA.cplx || dB.cplx || !dA.dbl || !dB.dbl || L.kara || L.kblk == 0 ||
+        L.kblk > 2048 || m == 0 || n == 0 || batch == 0 || batch > 65535)
+        return false;
+    FusedOperand a{}, b{};
+    a.X = static_cast<const double *>(dA.ptr);
+    a.ld = dA.ld;
+    a.nvec = m;
+    a.vpad = round_up(L.m_pad, 64);
+    a.plane = L.planeA;
+    a.vmax = L.m_pad;
+    a.sft = sftA;
+    a.out = outA;
+    b.X = static_cast<const double *>(dB.ptr);
+    b.ld = dB.ld;
+    b.nvec = n;
+    b.vpad = round_up(L.n_pad, 64);
+    b.plane = L.planeB;
+    b.vmax = L.n_pad;
+    b.sft = sftB;
+    b.out = outB;
+    const FusedBatch fb{strideA, strideB, L.m_pad, L.n_pad, L.N * L.planeA, L.N * L.planeB,
+                        batch > 1 && strideA == 0, batch > 1 && strideB == 0};
+    const size_t blocks = (a.vpad + b.vpad) / 4;
+    if (blocks > 0x7fffffff) return false;
+    const ModGroups G = make_groups(MP, L.N);
+    const dim3 grid((unsigned)blocks, (unsigned)batch), block(256);
+#define OZ2_FB1(K, CA, CB) launch(split_fused_batched_kernel<K, CA, CB>, grid, block, st, a, b, fb, len, L.ksteps, L.kblk, log2M, MP, G)
+#define OZ2_FB(K) do { if (dA.contig) { if (dB.contig) OZ2_FB1(K, true, true); else OZ2_FB1(K, true, false); } \
+                       else { if (dB.contig) OZ2_FB1(K, false, true); else OZ2_FB1(K, false, false); } } while (0)
+    if (L.kblk <= 1024) OZ2_FB(1024);
+    else if (L.kblk <= 1536) OZ2_FB(1536);
+    else OZ2_FB(2048);
+#undef OZ2_FB
+#undef OZ2_FB1
+    return true;
 }
 
 void split_finalize_accurate_pair(const int16_t *sft0A, const int32_t *boundA, size_t m, const int16_t *sft0B,

@@ -54,6 +54,11 @@ def _load():
     lib.gemmul8_work_size_lowmem.argtypes = [sz, sz, sz, u, i, u]
     lib.gemmul8_gemm_lowmem.restype = i
     lib.gemmul8_gemm_lowmem.argtypes = [p, i, i, sz, sz, sz, i, i, i, p, p, sz, p, sz, p, p, sz, u, i, p, i, u, d]
+    lib.gemmul8_work_size_strided_batched.restype = sz
+    lib.gemmul8_work_size_strided_batched.argtypes = [sz, sz, sz, u, i, sz]
+    lib.gemmul8_gemm_strided_batched.restype = i
+    lib.gemmul8_gemm_strided_batched.argtypes = [p, i, i, sz, sz, sz, i, i, i, p, p, sz, sz, p, sz, sz, p, p, sz, sz, sz,
+                                                 u, i, p, i, d]
     lib.gemmul8_timing_enable.argtypes = [i]
     lib.gemmul8_timing_read.argtypes = [d, ctypes.POINTER(ctypes.c_int)]
     lib.gemmul8_layout.argtypes = [sz, sz, sz, u, i, ctypes.POINTER(ctypes.c_size_t)]
@@ -146,6 +151,26 @@ def gemm(opA, opB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, num_moduli, fas
                               B.data_ptr(), ldb, be.ptr, C.data_ptr(), ldc, num_moduli, int(bool(fastmode)),
                               work.data_ptr(), computeType, pt)
     _check(rc)
+    return list(pt) if phase_times else None
+
+
+def workSize_strided_batched(m, n, k, num_moduli, batch, computeType=REAL_DEFAULT):
+    """Bytes of device workspace for gemm_strided_batched: the whole batch's (linear in batch)."""
+    return int(lib.gemmul8_work_size_strided_batched(m, n, k, num_moduli, computeType, batch))
+
+
+def gemm_strided_batched(opA, opB, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                         num_moduli, fastmode, work, computeType=REAL_DEFAULT, stream=None, phase_times=False):
+    """C[b] = alpha*op(A[b])*op(B[b]) + beta*C[b] for b < batch, element b at A + b*strideA, B + b*strideB,
+    C + b*strideC (elements; strideA or strideB may be 0), each bit-identical to gemm on that element.  Real
+    float64 in fast mode with round_up(k, 64) <= 2048 takes one split, one product and one CRT launch for the
+    batch; work holds workSize_strided_batched bytes.  Returns the phase times like gemm."""
+    ta, tb, tc = _DTYPE[A.dtype], _DTYPE[B.dtype], _DTYPE[C.dtype]
+    al, be = _scalar(alpha, C.dtype), _scalar(beta, C.dtype)
+    pt = (ctypes.c_double * 4)() if phase_times else None
+    _check(lib.gemmul8_gemm_strided_batched(_stream(stream), opA, opB, m, n, k, ta, tb, tc, al.ptr, A.data_ptr(), lda,
+                                            strideA, B.data_ptr(), ldb, strideB, be.ptr, C.data_ptr(), ldc, strideC,
+                                            batch, num_moduli, int(bool(fastmode)), work.data_ptr(), computeType, pt))
     return list(pt) if phase_times else None
 
 
@@ -333,6 +358,23 @@ def matmul(A, B, num_moduli=14, fastmode=True, out_dtype=None, work=None):
     else:
         gemm(OP_T, OP_T, m, n, k, 1.0, A, k, B, n, 0.0, Ct, m, num_moduli, fastmode, work, ct)
     return Ct.t()
+
+
+def bmm(A, B, num_moduli=14, fastmode=True, work=None):
+    """Row-major torch convenience beside matmul: A (batch x m x k) @ B (batch x k x n), real tensors, in one
+    strided-batched call (op T on both operands, no copies of contiguous inputs)."""
+    assert A.is_cuda and B.is_cuda and A.dim() == 3 and B.dim() == 3
+    assert A.shape[0] == B.shape[0] and A.shape[2] == B.shape[1] and not A.is_complex() and not B.is_complex()
+    A = A.contiguous()
+    B = B.contiguous()
+    batch, m, k = A.shape
+    n = B.shape[2]
+    Ct = torch.empty((batch, n, m), dtype=torch.promote_types(A.dtype, B.dtype), device=A.device)
+    if work is None:
+        work = torch.empty(workSize_strided_batched(m, n, k, num_moduli, batch), dtype=torch.uint8, device=A.device)
+    gemm_strided_batched(OP_T, OP_T, m, n, k, 1.0, A, k, m * k, B, n, k * n, 0.0, Ct, m, n * m, batch, num_moduli,
+                         fastmode, work)
+    return Ct.transpose(1, 2)
 
 
 # ---- instrumentation ----

@@ -81,6 +81,25 @@ int gemmul8_gemm_strided_batched(void *stream, int op_a, int op_b, size_t m, siz
                                  size_t ldc, size_t stride_c, size_t batch, unsigned num_moduli, int fastmode,
                                  void *work, int compute_type, double *phase_ns);
 
+/* --- symmetric rank-k update ---------------------------------------------------------------------
+ * trans = GEMMUL8_OP_N: C = alpha * A * A^T + beta * C with A n x k; GEMMUL8_OP_T: C = alpha * A^T * A + beta * C
+ * with A k x n; column-major.  Only the `uplo` triangle of the n x n C, diagonal included, is read (and only when
+ * beta != 0) and written; the other triangle and the ldc padding are never touched.  The triangle carries the
+ * same bits as gemmul8_gemm(trans, opposite op, n, n, k, A, A) writes there (BLAS epilogue semantics always:
+ * gemmul8_set_epilogue does not apply), and uplo = lower is the transpose of uplo = upper bit for bit.
+ * Fast mode splits op(A) once and multiplies the T (T + 1) / 2 tiles of the triangle per modulus (T = n / 256
+ * rounded up; "gemm_i8_syrk_kernel" / "gemm_i8_syrk_onetile_kernel"); accurate mode runs gemmul8_gemm's split.
+ * Padded k beyond 2^16 runs gemmul8_gemm's products over all tiles; the CRT is triangular either way.
+ * Real types only: type_a, type_c in {R_64F, R_32F} as gemmul8_gemm accepts them with type_b = type_a; a complex
+ * type returns GEMMUL8_E_TYPES, GEMMUL8_OP_C or an unknown uplo GEMMUL8_E_OP; moduli, size and leading-dimension
+ * checks are gemmul8_gemm's; n == 0 returns GEMMUL8_OK; on any error nothing is enqueued.  phase_ns as
+ * gemmul8_gemm.  gemmul8_work_size_syrk(n, k, N) == gemmul8_work_size(n, n, k, N, GEMMUL8_REAL_DEFAULT). */
+enum { GEMMUL8_FILL_LOWER = 0, GEMMUL8_FILL_UPPER = 1 };
+size_t gemmul8_work_size_syrk(size_t n, size_t k, unsigned num_moduli);
+int gemmul8_syrk(void *stream, int uplo, int trans, size_t n, size_t k, int type_a, int type_c, const void *alpha,
+                 const void *A, size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                 void *work, double *phase_ns);
+
 /* --- phase entry points (multi-GPU sharding, gemmul8/dist.py) ------------------------------------
  * gemmul8_gemm == gemmul8_split(0, N) + gemmul8_products(0, N) + gemmul8_recombine, on one stream.
  * Splitting the moduli range lets a rank produce only the residue planes [mod_begin, mod_end)
@@ -211,7 +230,9 @@ int gemmul8_get_epilogue(void);
 
 /* Name of the residue-product kernel the last products launch of this process took
  * ("gemm_i8_persistent_pg_kernel", "gemm_i8_persistent_kernel", "gemm_i8_kernel", "gemm_i8_small_kernel",
- * "gemm_i8_kernel (k-chunked)" or "none"). */
+ * "gemm_i8_kernel (k-chunked)", "gemm_i8_batched_kernel", "gemm_i8_batched_onetile_kernel", "gemm_i8_syrk_kernel",
+ * "gemm_i8_syrk_onetile_kernel" or "none"; a gemmul8_syrk call outside the triangular kernels' domain reports
+ * the gemm kernel that ran all tiles). */
 const char *gemmul8_last_products_kernel(void);
 
 /* --- bench / test harness (not part of the emulation path) ------------------------------------ */

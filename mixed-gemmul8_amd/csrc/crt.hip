@@ -518,6 +518,133 @@ void crt_inverse_batched(const uint8_t *R, const Layout &L, size_t batch, size_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// Triangular CRT (gemmul8_syrk): real outputs, 4 rows per lane, so a wave's 256 rows of column col are exactly
+// one tile row of the residue planes.  A wave whose tile lies wholly outside the triangle (lower: every row
+// < col; upper: every row > col) skips its loads, arithmetic and stores -- there is no block-level sync in the
+// loop -- and never touches a tile the triangular products left unwritten.  Where the diagonal crosses the
+// wave's rows, lanes with no row inside skip their residue loads (the words above the diagonal that the other
+// lanes load are valid: diagonal tiles are computed whole), elements outside the triangle are neither read
+// from C nor stored, and a 16-byte vector that straddles the diagonal takes the element path.  The value of
+// an element is crt_body.inc's: the same fma chains by (N, NUMM1), scaling and BLAS epilogue.
+template <int OT, bool NUMM1, unsigned N>
+__global__ __launch_bounds__(256) void crt_syrk_kernel(CrtArgs a, int upper) {
+    constexpr int R = 4;
+    using W = RowWord<R>;
+    using E = typename OutElem<OT>::T;
+    constexpr int EPV = 16 / sizeof(E);
+    __shared__ E buf[4][64 * R];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t wrow0 = ((size_t)blockIdx.x * 256 + wv * 64) * R;
+    if (wrow0 >= a.m) return;  // whole wave beyond the last row
+    const size_t r0 = wrow0 + (size_t)lane * R;
+    const int nr = r0 >= a.m ? 0 : (a.m - r0 >= R ? R : (int)(a.m - r0));
+    const bool plain_ab = a.ar == 1.0 && a.br == 0.0;
+    const bool zero_beta = a.br == 0.0;  // C is not read at beta = 0 (BLAS)
+    int16_t sa[R];
+#pragma unroll
+    for (int e = 0; e < R; ++e) sa[e] = e < nr ? a.sftA[r0 + e] : 0;
+    E *wb = buf[wv];
+    auto inside = [&](size_t row, size_t col) { return upper ? row <= col : row >= col; };
+    for (size_t col = blockIdx.y; col < a.n; col += gridDim.y) {
+        if (upper ? wrow0 > col : wrow0 + 64 * R <= col) continue;  // wave-uniform: the tile is outside
+        const int sB = a.sftB[col];
+        if (nr > 0 && (upper ? r0 <= col : r0 + R > col)) {
+            W w[N];
+            load_rows<N>(a, col * a.ldr + r0, nr == R, nr, w);
+            constexpr bool MO = OZ2_CRT_MODOUTER_ALL || N >= OZ2_CRT_MODOUTER_MIN_N;
+            if constexpr (MO) {
+                double vr[R];
+                crt_rows_const<N, NUMM1, R>(w, vr, std::make_integer_sequence<unsigned, N>{});
+#pragma unroll
+                for (int e = 0; e < R; ++e) {
+                    const double x = scalbn(vr[e], (int)sa[e] + sB);
+                    if constexpr (OT == 0) wb[crt_slot<E, R>(lane, e)] = x;
+                    else wb[crt_slot<E, R>(lane, e)] = __double2float_rn(x);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < R; ++e) {
+                    uint8_t r[N];
+#pragma unroll
+                    for (unsigned i = 0; i < N; ++i) r[i] = (uint8_t)(w[i] >> (8 * e));
+                    const double x = scalbn(crt_value_const<N, NUMM1>(r, std::make_integer_sequence<unsigned, N>{}),
+                                            (int)sa[e] + sB);
+                    if constexpr (OT == 0) wb[crt_slot<E, R>(lane, e)] = x;
+                    else wb[crt_slot<E, R>(lane, e)] = __double2float_rn(x);
+                }
+            }
+        }
+        wave_sync();
+        E *Cc = static_cast<E *>(a.C) + col * a.ldc + wrow0;
+        const bool vec_ok = (reinterpret_cast<uintptr_t>(Cc) & 15) == 0;
+#pragma unroll
+        for (int j = 0; j < R / EPV; ++j) {
+            const int idx = j * 64 * EPV + lane * EPV;
+            const size_t row = wrow0 + idx;
+            E v[EPV];
+            *reinterpret_cast<int4 *>(v) = *reinterpret_cast<const int4 *>(wb + crt_slot<E, R>(idx / R, idx % R));
+            if (vec_ok && row + EPV <= a.m && inside(upper ? row + EPV - 1 : row, col)) {
+                if (!plain_ab) {
+                    E c[EPV];
+                    if (zero_beta) {
+#pragma unroll
+                        for (int q = 0; q < EPV; ++q) c[q] = E{};
+                    } else {
+                        *reinterpret_cast<int4 *>(c) = *reinterpret_cast<const int4 *>(Cc + idx);
+                    }
+#pragma unroll
+                    for (int q = 0; q < EPV; ++q) v[q] = BlasEpi<OT>::template f<NUMM1>(v[q], c[q], a);
+                }
+                if (OZ2_CRT_NT & 2) {
+                    typedef int i4v __attribute__((ext_vector_type(4)));
+                    __builtin_nontemporal_store(*reinterpret_cast<const i4v *>(v), reinterpret_cast<i4v *>(Cc + idx));
+                } else {
+                    *reinterpret_cast<int4 *>(Cc + idx) = *reinterpret_cast<const int4 *>(v);
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < EPV; ++q) {
+                    if (row + q < a.m && inside(row + q, col)) {
+                        E x = v[q];
+                        if (!plain_ab) x = BlasEpi<OT>::template f<NUMM1>(x, zero_beta ? E{} : Cc[idx + q], a);
+                        Cc[idx + q] = x;
+                    }
+                }
+            }
+        }
+        wave_sync();
+    }
+}
+
+void crt_inverse_syrk(const uint8_t *R, const Layout &L, const int16_t *sftA, const int16_t *sftB, const CrtParams &CP,
+                      OutType ot, const void *alpha, const void *beta, void *C, size_t ldc, bool upper, hipStream_t st) {
+    CrtArgs a{};
+    a.R = R;
+    a.planeR = L.planeR;
+    a.ldr = L.ldr;
+    a.m = L.m;
+    a.n = L.n;
+    a.sftA = sftA;
+    a.sftB = sftB;
+    a.C = C;
+    a.ldc = ldc;
+    const bool f32 = ot == OutType::F32;
+    a.ar = f32 ? (double)*(const float *)alpha : *(const double *)alpha;
+    a.br = f32 ? (double)*(const float *)beta : *(const double *)beta;
+    const dim3 grid((unsigned)((L.m + 256 * 4 - 1) / (256 * 4)), (unsigned)(L.n < 65535 ? L.n : 65535));
+    const int up = upper ? 1 : 0;
+    switch (CP.N) {
+#define OZ2_N(n) case n: if (f32) launch(crt_syrk_kernel<1, true, n>, grid, dim3(256), st, a, up); \
+                         else if (CP.numM1) launch(crt_syrk_kernel<0, true, n>, grid, dim3(256), st, a, up); \
+                         else launch(crt_syrk_kernel<0, false, n>, grid, dim3(256), st, a, up); break;
+        OZ2_N(2) OZ2_N(3) OZ2_N(4) OZ2_N(5) OZ2_N(6) OZ2_N(7) OZ2_N(8) OZ2_N(9) OZ2_N(10) OZ2_N(11)
+        OZ2_N(12) OZ2_N(13) OZ2_N(14) OZ2_N(15) OZ2_N(16) OZ2_N(17) OZ2_N(18) OZ2_N(19) OZ2_N(20)
+#undef OZ2_N
+    default: break;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Partial CRT sums of a moduli range and the CRT finished from summed partials: the north star's
 // multi-GPU form (BASELINE.json: "a single RCCL reduce of partial FP64 accumulators"), gemmul8/dist.py
 // gemm_moduli_reduce.  A rank that holds the residue planes of moduli [j0, j1) writes per element

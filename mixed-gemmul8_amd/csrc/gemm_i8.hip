@@ -1611,6 +1611,317 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_batched_onetile_kernel(Ba
     epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, 0, true, u.q);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Symmetric rank-k residue products (gemmul8_syrk): the tiles of ONE triangle of the n_pad x n_pad residue
+// planes, T (T + 1) / 2 per modulus instead of T^2 (T = n_pad / 256).  The int8 products are exact, so the
+// residue of (i, j) equals that of (j, i): nothing of the other triangle is needed.  Row panel tm comes from
+// A's plane j and column panel tn from B's plane j; in fast mode both are the same plane (the slice layout of
+// A's rows and of B's columns is one layout, panel_offset).  Diagonal tiles are computed whole; the CRT masks
+// them.  A unit is (modulus j, raster position v); the raster is computed, no tile table in memory:
+// bands of 4 tile rows, each walked column by column clipped to the triangle (lower: tn <= tm), so a full band
+// b holds 16 b + 10 tiles and the ~32 tiles an XCD has in flight share about 4 row panels and 8 column panels,
+// as the gemm raster's 4 x 8 groups do.  uplo = upper is the same walk with (tm, tn) swapped: any (row panel,
+// column panel) pair is a valid tile of the shared plane.
+struct SyrkArgs {
+    GemmArgs g;      // mtiles = ntiles = T, nplanes = N
+    unsigned P;      // T (T + 1) / 2: tiles per plane
+    unsigned upper;  // 1: the tile of raster position (tm, tn) is (tn, tm)
+};
+struct SyrkUnit {
+    unsigned j, tm, tn;
+    uint32_t offA, offB;  // byte offsets of the tile's first panels in plane j of A and of B
+};
+// raster position v in [0, P) -> (tm, tn), tn <= tm < T; a scalar loop over at most T / 4 bands and 4 columns
+__device__ __forceinline__ void syrk_raster(unsigned T, unsigned v, unsigned &tm, unsigned &tn) {
+    unsigned r0 = 0, h = min(4u, T);  // the band's first tile row and its height
+    for (;;) {
+        const unsigned sz = r0 * h + h * (h + 1) / 2;  // r0 full columns of h tiles, then the band's own triangle
+        if (v < sz || r0 + 4 >= T) break;
+        v -= sz;
+        r0 += 4;
+        h = min(4u, T - r0);
+    }
+    if (v < r0 * h) {
+        tn = v / h;
+        tm = r0 + (v - tn * h);
+        return;
+    }
+    v -= r0 * h;
+    unsigned c = 0;
+    while (c + 1 < h && v >= h - c) {
+        v -= h - c;
+        ++c;
+    }
+    tn = r0 + c;
+    tm = tn + v;
+}
+__device__ __forceinline__ SyrkUnit syrk_unit(const SyrkArgs &a, unsigned j, unsigned v) {
+    SyrkUnit t;
+    unsigned lo_r, lo_c;
+    syrk_raster(a.g.mtiles, __builtin_amdgcn_readfirstlane(v), lo_r, lo_c);
+    // block-uniform: SGPRs
+    t.j = __builtin_amdgcn_readfirstlane(j);
+    t.tm = __builtin_amdgcn_readfirstlane(a.upper ? lo_c : lo_r);
+    t.tn = __builtin_amdgcn_readfirstlane(a.upper ? lo_r : lo_c);
+    t.offA = __builtin_amdgcn_readfirstlane((uint32_t)((size_t)t.tm * a.g.kstride * PANEL));
+    t.offB = __builtin_amdgcn_readfirstlane((uint32_t)((size_t)t.tn * a.g.kstride * PANEL));
+    return t;
+}
+
+// Persistent form (>= 6 k-steps): one block per CU, the per-group-epilogue kernel's pipeline -- 4-slot LDS-DMA
+// ring running three k-steps ahead across unit boundaries, the two wave groups one barrier apart for the whole
+// launch, each group parking and storing its own 128 rows, first MFMA of a unit from the bias splat, biased f64
+// residues, non-temporal stores.  The queues are the gemm kernel's, over the triangle: plane by plane, XCD x
+// takes a contiguous share of the plane's raster (P / 8 tiles, the first P mod 8 queues one more).  A block's
+// first two units are static (its rank on the XCD, then that plus the XCD's block count), later ones claimed
+// from the queue head two units ahead.
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_kernel(SyrkArgs a) {
+    static_assert(OZ2_MFMA16, "per-group epilogue: 16x16x64 accumulator map");
+    __shared__ __attribute__((aligned(1024))) int8_t smem[PLDS_BYTES + PARK_SPARE];
+    const GemmArgs &g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 2, wc = wave & 3;
+    uint32_t *const spare = reinterpret_cast<uint32_t *>(smem + PLDS_BYTES);
+    if (wr == 1) __builtin_amdgcn_s_setprio(1);
+
+    const unsigned G = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
+    const unsigned nblk = (G >> 3) + (xcd < (G & 7) ? 1u : 0u);
+    const unsigned q8 = a.P >> 3, r8 = a.P & 7;
+    const unsigned tx = q8 + (xcd < r8 ? 1u : 0u);  // this XCD's tiles of every plane, from raster position basex
+    const unsigned basex = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    const unsigned total = g.nplanes * tx;
+    auto unit_at = [&](unsigned i) {
+        const unsigned y = i / tx;
+        return syrk_unit(a, y, basex + (i - y * tx));
+    };
+    auto claim = [&]() { return __hip_atomic_fetch_add(g.queue + xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto to_unit = [&](unsigned pos) { return pos + 2 * nblk < total ? pos + 2 * nblk : NO_TILE; };
+    const unsigned ccur = (bid >> 3) < total ? (bid >> 3) : NO_TILE;
+    if (ccur == NO_TILE) return;  // block-uniform, before any barrier
+    if (tid == 0) {
+        const unsigned second = nblk + (bid >> 3);
+        spare[0] = second < total ? second : NO_TILE;
+    }
+
+    const unsigned K = g.ksteps;  // >= 6 (host)
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
+    const uint32_t lds_wave = lds_base + wave * 1024;
+    const uint32_t lane_off = wave * 1024 + lane * 16;
+    auto rsrcA = [&](const SyrkUnit &t) { return make_rsrc(g.A + (size_t)t.j * g.planeA, (uint32_t)g.planeA); };
+    auto rsrcB = [&](const SyrkUnit &t) { return make_rsrc(g.B + (size_t)t.j * g.planeB, (uint32_t)g.planeB); };
+    auto lo_of = [&](unsigned step) { return lds_wave + (step & (PSTAGES - 1)) * SLOT; };
+    auto rd_of = [&](unsigned step) { return smem + (step & (PSTAGES - 1)) * SLOT; };
+
+    SyrkUnit ct = unit_at(ccur);
+    v4si rA = rsrcA(ct), rB = rsrcB(ct);
+    constexpr unsigned D = PSTAGES - 1;
+    for (unsigned s0 = 0; s0 < D; ++s0) {
+        const uint32_t lo = lo_of(s0);
+        bglds16(rA, ct.offA + s0 * PANEL + lane_off, lo);
+        bglds16(rA, ct.offA + s0 * PANEL + lane_off + 8192, lo + 8192);
+        bglds16(rB, ct.offB + s0 * PANEL + lane_off, lo + PANEL);
+        bglds16(rB, ct.offB + s0 * PANEL + lane_off + 8192, lo + PANEL + 8192);
+    }
+    wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();  // step 0 landed (and the second unit's LDS write)
+    barrier();
+
+    unsigned s = 0;
+    unsigned cnext = __builtin_amdgcn_readfirstlane(spare[0]);
+    uint32_t da = ct.offA + D * PANEL, db = ct.offB + D * PANEL;
+    Frags f;
+    AccTile acc[ACC_I][ACC_J];
+    unsigned pos = 0;  // thread 0: the queue position claimed for the unit after next
+    bool claimed = false;
+    if (wr == 1) barrier();  // group 1 falls one barrier behind, for the whole launch
+    for (unsigned r = 0;; ++r) {
+        const v4i bias = v4i{} + g.bias[ct.j];
+        unsigned k = 0;
+        uint32_t na = 0, nb = 0;
+        v4si nrA = rA, nrB = rB;
+        auto step = [&](auto wait, auto first, auto mid) {
+            read_frags(f, rd_of(s), wr, wc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t lo = lo_of(s + D);
+            bglds16(rA, da + lane_off, lo);
+            bglds16(rA, da + lane_off + 8192, lo + 8192);
+            bglds16(rB, db + lane_off, lo + PANEL);
+            bglds16(rB, db + lane_off + 8192, lo + PANEL + 8192);
+            const bool jump = k + D + 1 == K;  // this unit's last step staged: on to the next unit's panels
+            da = jump ? na : da + PANEL;
+            db = jump ? nb : db + PANEL;
+            if (jump) {  // block-uniform
+                rA = nrA;
+                rB = nrB;
+            }
+            wait();
+            barrier();
+            if constexpr (decltype(first)::value) mfma_step_first(acc, f, bias);
+            else mfma_step<1>(acc, f);
+            mid();
+            barrier();
+        };
+        auto none = [] {};
+        // steps 0 and 1: from the second unit on, the previous unit's 8 residue stores are younger than the DMA
+        auto wait01 = [&] {
+            if (r > 0) wait_vm_lgkm0<GLDS_PER_STEP *(D - 1) + PARK_STORES>();
+            else wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+        };
+        step(wait01, std::true_type{}, [&] {
+            if (claimed) {  // group 0's MFMA interval: group 1 has read its parked residues back
+                unsigned p2 = pos;
+                asm volatile("" : "+v"(p2));
+                spare[0] = to_unit(p2);
+                __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0)
+            }
+        });
+        ++k, ++s;
+        step(wait01, std::false_type{}, none);
+        ++k, ++s;
+        if (r > 0) cnext = __builtin_amdgcn_readfirstlane(spare[0]);  // published by thread 0 two barriers ago
+        SyrkUnit nt = ct;
+        if (cnext != NO_TILE) {
+            nt = unit_at(cnext);
+            na = nt.offA;
+            nb = nt.offB;
+            nrA = rsrcA(nt);
+            nrB = rsrcB(nt);
+        }
+        const unsigned kend = cnext != NO_TILE ? K : K - D;
+        for (; k < kend; ++k, ++s) step([] { wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>(); }, std::false_type{}, none);
+        for (; k < K; ++k, ++s) {  // drain of the block's last unit
+            read_frags(f, rd_of(s), wr, wc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            wait_steps_lgkm0<GLDS_PER_STEP>(k + 2 < K ? (int)(K - k - 2) : 0);
+            barrier();
+            mfma_step<1>(acc, f);
+            barrier();
+        }
+
+        // ---- this group's epilogue: park interval, then store interval (the per-group kernel's layout) ----
+        claimed = tid == 0 && cnext != NO_TILE;
+        if (claimed) pos = claim();
+        int etid = tid;
+        asm volatile("" : "+v"(etid));
+        const int elane = etid & 63, gtid = etid & 255;
+        const int p = g.p[ct.j];
+        uint32_t *const park = wr == 0 ? reinterpret_cast<uint32_t *>(rd_of(s - 1)) : spare;
+        auto park_all = [&](auto &&res) {
+            const int t7 = elane & 7;
+            uint32_t *const pb = park + (wc * 64 + (elane & 15)) * 32 + (elane >> 4);
+#pragma unroll
+            for (int i = 0; i < ACC_I; ++i) {
+                uint32_t *const pi = pb + 4 * (i ^ t7);
+#pragma unroll
+                for (int jj = 0; jj < ACC_J; ++jj) {
+                    uint32_t w = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w |= res(acc[i][jj][e]) << (8 * e);
+                    pi[jj * 16 * 32] = w;
+                }
+            }
+        };
+        if (p == 256) {
+            park_all([&](int x) { return (uint32_t)x & 0xffu; });
+        } else {
+            const double invp = g.invp[ct.j], pneg = -(double)p;
+            const double cneg = __builtin_fma(-0x1p52, invp, 0x1p-8);
+            park_all([&](int x) { return residue_biased_f64((uint32_t)x, invp, cneg, pneg); });
+        }
+        __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0), vmcnt untouched
+        barrier();
+        uint8_t *out = static_cast<uint8_t *>(g.out) + (size_t)ct.j * g.planeOut + (size_t)ct.tn * 256 * g.ldo +
+                       (size_t)ct.tm * 256 + wr * 128;
+#pragma unroll
+        for (int it = 0; it < PARK_STORES; ++it) {
+            const int chunk = gtid + 256 * it;
+            const int col = chunk >> 3, c = chunk & 7;
+            const uint4 v = *reinterpret_cast<const uint4 *>(park + col * 32 + ((c ^ (col & 7)) << 2));
+            typedef unsigned u4v __attribute__((ext_vector_type(4)));
+            const u4v val = u4v{v.x, v.y, v.z, v.w};
+            u4v *dst = reinterpret_cast<u4v *>(out + (size_t)col * g.ldo + 16 * c);
+            if (OZ2_RES_NTS) __builtin_nontemporal_store(val, dst);
+            else *dst = val;
+        }
+        if (claimed) asm volatile("" ::"v"(pos));  // the claim returned (older than the 8 stores: vmcnt(8))
+        __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // park reads done
+        barrier();
+        if (cnext == NO_TILE) break;
+        ct = nt;
+    }
+    if (wr == 0) barrier();  // group 0 passed one barrier fewer (group 1's initial one)
+}
+
+// One-unit form (fewer than 6 k-steps, or fewer than 3 units per CU): grid (P, N), block x of plane y computes
+// the tile at raster position wgid(x) -- the gemm one-tile kernel's XCD remap, so the blocks an XCD receives are
+// a contiguous share of the plane's raster -- with the one-tile kernel's ring, ping-pong main loop and epilogue.
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_onetile_kernel(SyrkArgs a) {
+    __shared__ __attribute__((aligned(1024))) int8_t smem[LDS_BYTES];
+    const GemmArgs &g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 2, wc = wave & 3;
+    const unsigned nwg = gridDim.x, bid = blockIdx.x;
+    const unsigned xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const SyrkUnit u = syrk_unit(a, blockIdx.y, wgid);
+
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
+    const uint32_t lds_wave = lds_base + wave * 1024;
+    const v4si rA = make_rsrc(g.A + (size_t)u.j * g.planeA, (uint32_t)g.planeA);
+    const v4si rB = make_rsrc(g.B + (size_t)u.j * g.planeB, (uint32_t)g.planeB);
+    const uint32_t oA = u.offA + wave * 1024 + lane * 16, oB = u.offB + wave * 1024 + lane * 16;
+    auto stage = [&](unsigned ks, unsigned slot) {
+        const uint32_t g32 = ks * (uint32_t)PANEL, lo = lds_wave + slot * SLOT;
+        bglds16(rA, oA + g32, lo);
+        bglds16(rA, oA + g32 + 8192, lo + 8192);
+        bglds16(rB, oB + g32, lo + PANEL);
+        bglds16(rB, oB + g32 + 8192, lo + PANEL + 8192);
+    };
+
+    AccTile acc[ACC_I][ACC_J];
+    const int acc0 = g.bias[u.j];
+#pragma unroll
+    for (int i = 0; i < ACC_I; ++i)
+#pragma unroll
+        for (int jj = 0; jj < ACC_J; ++jj) acc[i][jj] = AccTile{} + acc0;
+
+    const unsigned K = g.ksteps;  // >= 1 (host)
+    constexpr unsigned D = STAGES - 1;
+    // barrier accounting as gemm_i8_kernel: 1 + 2K + 1 per group before the epilogue
+    for (unsigned s0 = 0; s0 < D; ++s0)
+        if (s0 < K) stage(s0, s0);
+    if (K >= D) wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+    else wait_steps_lgkm0<GLDS_PER_STEP>((int)K - 1);
+    barrier();
+    if (wr == 1) barrier();
+    Frags f;
+    unsigned slot_cur = 0, slot_issue = D % STAGES, t = 0;
+    for (; t + D < K; ++t) {  // steady state
+        read_frags(f, smem + slot_cur * SLOT, wr, wc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        stage(t + D, slot_issue);
+        wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+        barrier();
+        mfma_step(acc, f);
+        barrier();
+        slot_cur = slot_cur == STAGES - 1 ? 0 : slot_cur + 1;
+        slot_issue = slot_issue == STAGES - 1 ? 0 : slot_issue + 1;
+    }
+    for (; t < K; ++t) {  // drain
+        read_frags(f, smem + slot_cur * SLOT, wr, wc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        wait_steps_lgkm0<GLDS_PER_STEP>(t + 2 < K ? (int)(K - t - 2) : 0);
+        barrier();
+        mfma_step(acc, f);
+        barrier();
+        slot_cur = slot_cur == STAGES - 1 ? 0 : slot_cur + 1;
+    }
+    if (wr == 0) barrier();
+    barrier();  // all waves done with the ring before the epilogue reuses it
+    epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, 0, true, u.j);
+}
+
 // Exhaustive check of the two residue epilogues against exact arithmetic, every input and every
 // modulus: path 0 = biased (x in [-2^30, 2^30], the accumulator starting at bias_i), path 1 = signed
 // Barrett (every int32, conv_32i_2_8u.hpp:7-56).  Counts mismatches into *count.
@@ -1973,6 +2284,62 @@ bool gemm_i8_batched(const int8_t *A8, const int8_t *B8, const Layout &L, unsign
     } else {
         g_last_residue_kernel.store(7, std::memory_order_relaxed);
         launch(gemm_i8_batched_onetile_kernel, dim3((unsigned)(8 * longest)), dim3(NTHREADS), st, a);
+    }
+    return true;
+}
+
+bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
+    const size_t T = L.mtiles, P = T * (T + 1) / 2, units = P * N;
+    const char *ff = getenv("GEMMUL8_FORCE_FLAT_DMA");
+    // a square problem, buffer descriptors (planes < 4 GiB), the biased residue path, 32-bit unit counts
+    if (L.nsub != 1 || L.mtiles != L.ntiles || L.ksteps == 0 || L.k_pad > ((size_t)1 << 16) ||
+        L.planeA >= ((size_t)1 << 32) || L.planeB >= ((size_t)1 << 32) || (ff && atoi(ff)) || N == 0 || N > 65535 ||
+        units == 0 || units > 0x0fffffffu)
+        return false;
+    SyrkArgs a{};
+    GemmArgs &g = a.g;
+    g.A = A8;
+    g.B = B8;
+    g.planeA = L.planeA;
+    g.planeB = L.planeB;
+    g.ksteps = g.kstride = (unsigned)L.ksteps;
+    g.mtiles = g.ntiles = (unsigned)T;
+    g.nplanes = N;
+    g.out = R;
+    g.planeOut = L.planeR;
+    g.ldo = L.ldr;
+    g.nsub = 1;
+    g.biased = 1;
+    for (int i = 0; i < OZ2_MAX_MODULI; ++i) {
+        g.p[i] = MP.p[i];
+        g.barrett[i] = MP.barrett[i];
+        const uint32_t p = MP.p[i] > 0 ? (uint32_t)MP.p[i] : 256u;
+        g.minv[i] = (uint32_t)((((uint64_t)1) << 32) / p);
+        g.bias[i] = (int)(((((uint64_t)1) << 30) + p - 1) / p * p);
+        g.invp[i] = 1.0 / (double)p;
+    }
+    g.queue = queue;
+    a.P = (unsigned)P;
+    a.upper = upper ? 1u : 0u;
+    g_last_tail_small.store(0, std::memory_order_relaxed);
+    // gemm's rule over the triangle's units: persistent from 3 units per CU (GEMMUL8_PERSISTENT=0 / 1: never /
+    // wherever the kernel applies), the one-unit launch below that
+    const unsigned ncu = device_cu_count();
+    const int pmode = persistent_mode();
+    if (queue && g.ksteps >= 6 && pmode != 0 && (pmode == 1 || units >= 3 * (size_t)ncu)) {
+        if (!queue_zeroed) zero_i32(reinterpret_cast<int32_t *>(queue), 8, st);
+        // GEMMUL8_PERSISTENT_GRID caps the grid as it does for gemm_i8, at no fewer than 8 blocks (one per queue)
+        static const unsigned grid_cap = [] {
+            const char *e = getenv("GEMMUL8_PERSISTENT_GRID");
+            return e ? (unsigned)atoi(e) : 0u;
+        }();
+        const unsigned grid = (unsigned)std::min<size_t>(units, std::min(ncu, grid_cap ? std::max(grid_cap, 8u) : ncu));
+        g_last_residue_kernel.store(8, std::memory_order_relaxed);
+        launch(gemm_i8_syrk_kernel, dim3(grid), dim3(NTHREADS), st, a);
+    } else {
+        g_last_residue_kernel.store(9, std::memory_order_relaxed);
+        launch(gemm_i8_syrk_onetile_kernel, dim3((unsigned)P, N), dim3(NTHREADS), st, a);
     }
     return true;
 }

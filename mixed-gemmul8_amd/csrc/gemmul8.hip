@@ -681,10 +681,103 @@ static int run_batched(const Call &c, size_t strideA, size_t strideB, size_t str
     return GEMMUL8_OK;
 }
 
+// ---------------- symmetric rank-k update ----------------
+// c describes gemm(trans, opposite op, n, n, k, A, A): both operand descriptors are the same, so the shifts and
+// slices of op(A)'s rows are what gemm computes for either operand.  Fast mode splits that one operand once
+// (the single-operand launches, on the caller's stream; the encode zeroes the tile-queue heads) and hands the
+// A planes and sftA to the products and the CRT twice.  Accurate mode runs phase_split unchanged -- the bound
+// product couples the two shift vectors -- and passes both regions on.  The products are the triangle's tiles
+// (gemm_i8_syrk), or outside their domain every tile through gemm_i8; the CRT is the triangular one either way.
+static int run_syrk(Call &c, bool upper, double *phase_ns) {
+    const Views v = views(c.work, c.n, c.n, c.k, c.N, false);
+    const Layout &L = v.L;
+    const bool capturing = is_capturing(c.st);
+    if (phase_ns && capturing)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    const bool want_events = phase_ns != nullptr && !capturing;
+    bool record;
+    timing::Rec rec{};
+    {
+        std::lock_guard<std::mutex> g(timing::mu);
+        record = want_events || (timing::enabled && !capturing);
+        if (record) rec = timing::acquire();
+    }
+    auto fail = [&]() {
+        if (record) {
+            std::lock_guard<std::mutex> g(timing::mu);
+            timing::pool.push_back(rec);
+        }
+        return GEMMUL8_E_HIP;
+    };
+    const int8_t *B8 = c.fast ? v.A8 : v.B8;
+    const int16_t *sftB = c.fast ? v.sftA : v.sftB;
+    {
+        timing::Phase split(record, c.st, rec.start, nullptr);
+        if (c.fast) {
+            operand_shifts(c, v, true, c.st);
+            operand_encode(c, v, true, 0, c.N, 0, c.st);
+        } else {
+            phase_split(c, v, 0, c.N, false);
+        }
+        split.end();
+    }
+    if (!launch_ok()) return fail();
+    {
+        timing::Phase prod(record, c.st, rec.prod0, rec.prod1);
+        const ModParams MP = make_mod_params(c.N);
+        if (!gemm_i8_syrk(v.A8, B8, L, c.N, upper, v.R, MP, c.st, v.queue, true))
+            gemm_i8(v.A8, B8, L, c.N, Epi::RESIDUE, v.R, nullptr, nullptr, MP, c.st, v.queue, true);
+        prod.end();
+    }
+    if (!launch_ok()) return fail();
+    {
+        timing::Phase crt(record, c.st, nullptr, rec.crt1);
+        crt_inverse_syrk(v.R, L, v.sftA, sftB, make_crt_params(c.N, c.ot == OutType::F32), c.ot, c.alpha, c.beta, c.C,
+                         c.ldc, upper, c.st);
+        crt.end();
+    }
+    if (!launch_ok()) return fail();
+    if (want_events) {
+        float t[4];
+        timing::read(rec, t);
+        for (int i = 0; i < 4; ++i) phase_ns[i] = t[i] * 1e6;
+    }
+    if (record) {
+        std::lock_guard<std::mutex> g(timing::mu);
+        if (timing::enabled) timing::pending.push_back(rec);
+        else timing::pool.push_back(rec);
+    }
+    return GEMMUL8_OK;
+}
+
 }  // namespace oz2
 
 // =============================== C ABI ===================================
 extern "C" {
+
+size_t gemmul8_work_size_syrk(size_t n, size_t k, unsigned num_moduli) {
+    return oz2::make_layout(n, n, k, num_moduli, false).total;
+}
+
+int gemmul8_syrk(void *stream, int uplo, int trans, size_t n, size_t k, int type_a, int type_c, const void *alpha,
+                 const void *A, size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                 void *work, double *phase_ns) {
+    if (num_moduli < 2 || num_moduli > 20) return GEMMUL8_E_MODULI;
+    if (type_a < 0 || type_a > 3 || type_c < 0 || type_c > 3 || oz2::dt_cplx(type_a) || oz2::dt_cplx(type_c))
+        return GEMMUL8_E_TYPES;
+    if ((trans != GEMMUL8_OP_N && trans != GEMMUL8_OP_T) || (uplo != GEMMUL8_FILL_LOWER && uplo != GEMMUL8_FILL_UPPER))
+        return GEMMUL8_E_OP;
+    oz2::Call c{};
+    const int rc = oz2::prepare(stream, trans, trans == GEMMUL8_OP_N ? GEMMUL8_OP_T : GEMMUL8_OP_N, n, n, k, type_a,
+                                type_a, type_c, alpha, A, lda, A, lda, beta, C, ldc, num_moduli, fastmode, work,
+                                GEMMUL8_REAL_DEFAULT, c);
+    if (rc != GEMMUL8_OK) return rc;
+    if (phase_ns)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    if (n == 0) return GEMMUL8_OK;
+    oz2::clear_stale_error();
+    return oz2::run_syrk(c, uplo == GEMMUL8_FILL_UPPER, phase_ns);
+}
 
 size_t gemmul8_work_size_strided_batched(size_t m, size_t n, size_t k, unsigned num_moduli, int compute_type,
                                          size_t batch) {
@@ -1003,6 +1096,8 @@ const char *gemmul8_last_products_kernel(void) {
     case 5: return tail ? "gemm_i8_persistent_pg_kernel+gemm_i8_small_kernel" : "gemm_i8_persistent_pg_kernel";
     case 6: return "gemm_i8_batched_kernel";
     case 7: return "gemm_i8_batched_onetile_kernel";
+    case 8: return "gemm_i8_syrk_kernel";
+    case 9: return "gemm_i8_syrk_onetile_kernel";
     default: return "none";
     }
 }

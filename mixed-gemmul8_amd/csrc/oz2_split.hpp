@@ -155,9 +155,16 @@ void gemm_i8(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned nplan
 bool gemm_i8_batched(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, size_t batch, bool shareA,
                      bool shareB, uint8_t *R, const ModParams &MP, hipStream_t st, uint32_t *queue,
                      bool queue_zeroed);
+// Residue products of one triangle of a square problem (gemmul8_syrk; gemm_i8_syrk_kernel /
+// gemm_i8_syrk_onetile_kernel): the tiles (tm, tn) with tn <= tm (upper: tm <= tn) of the N residue planes R, row
+// panels from A8's planes and column panels from B8's (the same pointer in fast mode); queue as gemm_i8.
+// false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB or forced flat DMA)
+bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed);
 // the residue-product kernel of the last RESIDUE launch: 0 none yet, 1 one-tile (gemm_i8_kernel),
 // 2 persistent (gemm_i8_persistent_kernel), 3 k-chunked one-tile launches, 4 128 x 128 (gemm_i8_small_kernel),
-// 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit; g_last_tail_small: its last planes ran as 128 x 128 tiles
+// 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit, 8 / 9 SYRK
+// persistent / one-unit; g_last_tail_small: its last planes ran as 128 x 128 tiles
 extern std::atomic<int> g_last_residue_kernel;
 extern std::atomic<int> g_last_tail_small;
 // exhaustive exactness check of the residue epilogues (0 = biased, 1 = signed): mismatch count
@@ -175,6 +182,11 @@ void crt_inverse_batched(const uint8_t *R, const Layout &L, size_t batch, size_t
                          size_t strideSA, const int16_t *sftB, size_t strideSB, const CrtParams &CP,
                          const void *alpha, const void *beta, void *C, size_t ldc, size_t strideC, hipStream_t st,
                          int ref_epi);
+
+// real CRT of one triangle of a square problem (gemmul8_syrk; crt_syrk_kernel, BLAS epilogue): column col's rows
+// >= col (upper: <= col) only; nothing outside the triangle is read from R or C or written
+void crt_inverse_syrk(const uint8_t *R, const Layout &L, const int16_t *sftA, const int16_t *sftB, const CrtParams &CP,
+                      OutType ot, const void *alpha, const void *beta, void *C, size_t ldc, bool upper, hipStream_t st);
 
 // partial CRT sums of moduli [j0, j1) into S ([2][n][lds]: C1 then C2) and the CRT finished from summed
 // partials (real outputs; gemmul8_crt_partial / gemmul8_crt_finish)

@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libgemmul8_amd.so")
 
 REAL_DEFAULT, COMPLEX_BIG_MATRIX_ENCODE, COMPLEX_CLASSIC_MULT, COMPLEX_KARATSUBA_MULT = 0, 1, 2, 3
 OP_N, OP_T, OP_C = 0, 1, 2
+FILL_LOWER, FILL_UPPER = 0, 1
 R_64F, R_32F, C_64F, C_32F = 0, 1, 2, 3
 _DTYPE = {torch.float64: R_64F, torch.float32: R_32F, torch.complex128: C_64F, torch.complex64: C_32F}
 _ERR = {-1: "num_moduli outside [2, 20]", -2: "unsupported dtype combination for computeType",
@@ -59,6 +60,10 @@ def _load():
     lib.gemmul8_gemm_strided_batched.restype = i
     lib.gemmul8_gemm_strided_batched.argtypes = [p, i, i, sz, sz, sz, i, i, i, p, p, sz, sz, p, sz, sz, p, p, sz, sz, sz,
                                                  u, i, p, i, d]
+    lib.gemmul8_work_size_syrk.restype = sz
+    lib.gemmul8_work_size_syrk.argtypes = [sz, sz, u]
+    lib.gemmul8_syrk.restype = i
+    lib.gemmul8_syrk.argtypes = [p, i, i, sz, sz, i, i, p, p, sz, p, p, sz, u, i, p, d]
     lib.gemmul8_timing_enable.argtypes = [i]
     lib.gemmul8_timing_read.argtypes = [d, ctypes.POINTER(ctypes.c_int)]
     lib.gemmul8_layout.argtypes = [sz, sz, sz, u, i, ctypes.POINTER(ctypes.c_size_t)]
@@ -171,6 +176,24 @@ def gemm_strided_batched(opA, opB, m, n, k, alpha, A, lda, strideA, B, ldb, stri
     _check(lib.gemmul8_gemm_strided_batched(_stream(stream), opA, opB, m, n, k, ta, tb, tc, al.ptr, A.data_ptr(), lda,
                                             strideA, B.data_ptr(), ldb, strideB, be.ptr, C.data_ptr(), ldc, strideC,
                                             batch, num_moduli, int(bool(fastmode)), work.data_ptr(), computeType, pt))
+    return list(pt) if phase_times else None
+
+
+def workSize_syrk(n, k, num_moduli):
+    """Bytes of device workspace for syrk: workSize(n, n, k, num_moduli)."""
+    return int(lib.gemmul8_work_size_syrk(n, k, num_moduli))
+
+
+def syrk(uplo, trans, n, k, alpha, A, lda, beta, C, ldc, num_moduli, fastmode, work, stream=None, phase_times=False):
+    """The `uplo` triangle (FILL_LOWER / FILL_UPPER, diagonal included) of C = alpha*A*A^T + beta*C (trans = OP_N,
+    A n x k) or alpha*A^T*A + beta*C (OP_T, A k x n) on column-major real device buffers; the other triangle of C
+    is neither read nor written.  The triangle has the bits gemm(trans, the opposite op, n, n, k, ..., A, A, ...)
+    writes there.  work holds workSize_syrk bytes.  Returns the phase times like gemm."""
+    ta, tc = _DTYPE[A.dtype], _DTYPE[C.dtype]
+    al, be = _scalar(alpha, C.dtype), _scalar(beta, C.dtype)
+    pt = (ctypes.c_double * 4)() if phase_times else None
+    _check(lib.gemmul8_syrk(_stream(stream), uplo, trans, n, k, ta, tc, al.ptr, A.data_ptr(), lda, be.ptr,
+                            C.data_ptr(), ldc, num_moduli, int(bool(fastmode)), work.data_ptr(), pt))
     return list(pt) if phase_times else None
 
 

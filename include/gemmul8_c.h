@@ -100,6 +100,31 @@ int gemmul8_syrk(void *stream, int uplo, int trans, size_t n, size_t k, int type
                  const void *A, size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
                  void *work, double *phase_ns);
 
+/* --- Hermitian rank-k update ---------------------------------------------------------------------
+ * trans = GEMMUL8_OP_N: C = alpha * A * A^H + beta * C with A n x k; GEMMUL8_OP_C: C = alpha * A^H * A + beta * C
+ * with A k x n; column-major, complex.  alpha and beta point to one REAL host value of C's precision (double for
+ * C_64F, float for C_32F), as in BLAS zherk / cherk.  Only the `uplo` triangle of the n x n C, diagonal included,
+ * is read (and only when beta != 0) and written; the other triangle and the ldc padding are never touched.
+ * Off the diagonal the triangle carries the bits gemmul8_gemm(trans, opposite op (N <-> C), n, n, k, A, A) writes
+ * there with alpha = (alpha, 0), beta = (beta, 0) and any complex compute type (accurate mode:
+ * GEMMUL8_COMPLEX_KARATSUBA_MULT or CLASSIC_MULT, whose bound carries no reference defect); BLAS epilogue semantics
+ * always (gemmul8_set_epilogue does not apply).  On the diagonal the imaginary part of C is not read and is written
+ * as +0.0, and the real part carries gemmul8_gemm's bits for a C whose diagonal imaginary parts are +0.0.  The two
+ * `uplo` results are each pinned to gemmul8_gemm's own triangle; that one is the conjugate transpose of the other
+ * bit for bit is not promised.
+ * The products always run on the Karatsuba geometry: per modulus the T (T + 1) / 2 tiles of the triangle of each
+ * of the three sub-products (T = n / 256 rounded up; "gemm_i8_herk_kernel" / "gemm_i8_herk_onetile_kernel").
+ * Padded k beyond 2^16 runs gemmul8_gemm's products over all tiles; the CRT is triangular either way.
+ * Complex types only: type_a, type_c in {C_64F, C_32F} as gemmul8_gemm accepts them with type_b = type_a; a real
+ * type returns GEMMUL8_E_TYPES, GEMMUL8_OP_T or an unknown uplo GEMMUL8_E_OP; moduli, size and leading-dimension
+ * checks are gemmul8_gemm's; n == 0 returns GEMMUL8_OK; on any error nothing is enqueued.  phase_ns as
+ * gemmul8_gemm.  gemmul8_work_size_herk(n, k, N) is the Karatsuba layout's size at every shape (==
+ * gemmul8_work_size(n, n, k, N, GEMMUL8_COMPLEX_KARATSUBA_MULT) wherever gemmul8_gemm takes that geometry). */
+size_t gemmul8_work_size_herk(size_t n, size_t k, unsigned num_moduli);
+int gemmul8_herk(void *stream, int uplo, int trans, size_t n, size_t k, int type_a, int type_c, const void *alpha,
+                 const void *A, size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                 void *work, double *phase_ns);
+
 /* --- phase entry points (multi-GPU sharding, gemmul8/dist.py) ------------------------------------
  * gemmul8_gemm == gemmul8_split(0, N) + gemmul8_products(0, N) + gemmul8_recombine, on one stream.
  * Splitting the moduli range lets a rank produce only the residue planes [mod_begin, mod_end)
@@ -231,8 +256,8 @@ int gemmul8_get_epilogue(void);
 /* Name of the residue-product kernel the last products launch of this process took
  * ("gemm_i8_persistent_pg_kernel", "gemm_i8_persistent_kernel", "gemm_i8_kernel", "gemm_i8_small_kernel",
  * "gemm_i8_kernel (k-chunked)", "gemm_i8_batched_kernel", "gemm_i8_batched_onetile_kernel", "gemm_i8_syrk_kernel",
- * "gemm_i8_syrk_onetile_kernel" or "none"; a gemmul8_syrk call outside the triangular kernels' domain reports
- * the gemm kernel that ran all tiles). */
+ * "gemm_i8_syrk_onetile_kernel", "gemm_i8_herk_kernel", "gemm_i8_herk_onetile_kernel" or "none"; a gemmul8_syrk or
+ * gemmul8_herk call outside the triangular kernels' domain reports the gemm kernel that ran all tiles). */
 const char *gemmul8_last_products_kernel(void);
 
 /* --- bench / test harness (not part of the emulation path) ------------------------------------ */

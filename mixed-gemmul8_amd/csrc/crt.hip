@@ -645,6 +645,164 @@ void crt_inverse_syrk(const uint8_t *R, const Layout &L, const int16_t *sftA, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// Triangular complex CRT (gemmul8_herk) over the Karatsuba sub-planes P1, P2, P3 of a square problem.
+// Work mapping: 4 rows per lane, so a wave's 256 rows of a column are one tile row of the residue planes, and a
+// block's 4 waves are 4 consecutive tile rows of `cols` adjacent columns (one column group, blockIdx.y; cols
+// divides 256, so a group lies in one column tile tc).  The tile rows are numbered FROM THE DIAGONAL
+// TILE of the group: wave w = 4 blockIdx.x + wave-in-block is tile row tc + w (upper: tc - w).  The live waves of
+// a column group are therefore the first T - tc (upper: tc + 1) of the 4 ceil(T / 4) launched, packed into its
+// first blocks; every other block fails one scalar compare and leaves, and at most 3 waves idle per column group
+// where crt_syrk_kernel (rows numbered from 0, one column per block) idles half the waves of half its blocks.
+// A wave outside the triangle loads nothing: the products left those residue tiles unwritten.  Only w = 0 is a
+// diagonal tile; there lanes with no row inside skip their loads (the words of a live lane that reach across the
+// diagonal are valid: diagonal tiles are computed whole), elements outside the triangle are neither read from C
+// nor stored, and a 16-byte vector (two complex floats) that straddles the diagonal takes the element path.  The
+// diagonal element takes +0.0 for C's imaginary part and stores +0.0 as its own.
+// Arithmetic: crt_body.inc's KARA branch statement for statement -- Re from the P1 and P2 words, P3's loads in
+// flight under it, then Im -- with the same chains by (N, NUMM1), scaling and BlasEpi, alpha = (ar, 0), beta = (br, 0).
+template <int OT, bool NUMM1, unsigned N>
+__global__ __launch_bounds__(256) void crt_herk_kernel(CrtArgs a, int upper, unsigned cols) {
+    static_assert(OT >= 2, "complex outputs");
+    constexpr int R = 4;
+    using W = RowWord<R>;
+    using E = typename OutElem<OT>::T;
+    constexpr int EPV = 16 / sizeof(E);
+    __shared__ E buf[4][64 * R];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t T = (a.m + 255) >> 8;
+    const size_t w = (size_t)blockIdx.x * 4 + wv;  // this wave's distance from the diagonal tile, in tile rows
+    const bool plain_ab = a.ar == 1.0 && a.br == 0.0;
+    const bool zero_beta = a.br == 0.0;  // C is not read at beta = 0 (BLAS)
+    E *wb = buf[wv];
+    for (size_t col0 = (size_t)blockIdx.y * cols; col0 < a.n; col0 += (size_t)gridDim.y * cols) {
+        const size_t tc = col0 >> 8;
+        if (upper ? w > tc : tc + w >= T) continue;  // wave-uniform: no tile row w from the diagonal in the triangle
+        const size_t wrow0 = (upper ? tc - w : tc + w) << 8;
+        const size_t r0 = wrow0 + (size_t)lane * R;
+        const int nr = r0 >= a.m ? 0 : (a.m - r0 >= R ? R : (int)(a.m - r0));
+        const bool diag = w == 0;
+        int16_t sa[R];
+#pragma unroll
+        for (int e = 0; e < R; ++e) sa[e] = e < nr ? a.sftA[r0 + e] : 0;
+        auto inside = [&](size_t row, size_t col) { return !diag || (upper ? row <= col : row >= col); };
+        for (size_t col = col0; col < col0 + cols && col < a.n; ++col) {
+            const int sB = a.sftB[col];
+            if (nr > 0 && inside(upper ? r0 : r0 + R - 1, col)) {
+                // whole words: r0 is a multiple of 4 below m, and the planes are padded and computed to 256 rows
+                const size_t off = col * a.ldr + r0;
+                W wr[N], wi[N], w1[N], w2[N];
+                load_rows<N>(a, off, true, R, w1);
+                load_rows<N>(a, off + a.sub, true, R, w2);
+                kara_pair_words<N>(w1, w2, wr, wi, std::make_integer_sequence<unsigned, N>{});
+                size_t off3 = off + 2 * a.sub;
+                asm volatile("" : "+v"(off3) : "v"(wi[N - 1]));  // P3's loads go out after the combination
+                W w3[N];
+                load_rows<N>(a, off3, true, R, w3);
+                double v[R];
+                crt_rows_const<N, NUMM1, R>(wr, v, std::make_integer_sequence<unsigned, N>{});
+#pragma unroll
+                for (int e = 0; e < R; ++e) {
+                    const double vr = scalbn(v[e], (int)sa[e] + sB);
+                    if constexpr (OT == 2) wb[crt_slot<E, R>(lane, e)].x = vr;
+                    else wb[crt_slot<E, R>(lane, e)].x = __double2float_rn(vr);
+                }
+                asm volatile("" ::: "memory");  // the real parts go to LDS now
+                kara_sub_words<N>(w3, wi, std::make_integer_sequence<unsigned, N>{});
+                crt_rows_const<N, NUMM1, R>(wi, v, std::make_integer_sequence<unsigned, N>{});
+#pragma unroll
+                for (int e = 0; e < R; ++e) {
+                    const double vi = scalbn(v[e], (int)sa[e] + sB);
+                    if constexpr (OT == 2) wb[crt_slot<E, R>(lane, e)].y = vi;
+                    else wb[crt_slot<E, R>(lane, e)].y = __double2float_rn(vi);
+                }
+            }
+            wave_sync();
+            E *Cc = static_cast<E *>(a.C) + col * a.ldc + wrow0;
+            const bool vec_ok = (reinterpret_cast<uintptr_t>(Cc) & 15) == 0;
+            // element x of row `row` through the epilogue; on the diagonal C's imaginary part counts as +0.0 and
+            // the result's is +0.0
+            auto finish = [&](E x, E c, size_t row) {
+                const bool d = diag && row == col;
+                if (d) c.y = 0;
+                if (!plain_ab) x = BlasEpi<OT>::template f<NUMM1>(x, c, a);
+                if (d) x.y = 0;
+                return x;
+            };
+#pragma unroll
+            for (int j = 0; j < R / EPV; ++j) {
+                const int idx = j * 64 * EPV + lane * EPV;
+                const size_t row = wrow0 + idx;
+                E x[EPV];
+                *reinterpret_cast<int4 *>(x) = *reinterpret_cast<const int4 *>(wb + crt_slot<E, R>(idx / R, idx % R));
+                if (vec_ok && row + EPV <= a.m && inside(upper ? row + EPV - 1 : row, col)) {
+                    E c[EPV];
+                    if (plain_ab || zero_beta) {
+#pragma unroll
+                        for (int q = 0; q < EPV; ++q) c[q] = E{};
+                    } else {
+                        *reinterpret_cast<int4 *>(c) = *reinterpret_cast<const int4 *>(Cc + idx);
+                    }
+#pragma unroll
+                    for (int q = 0; q < EPV; ++q) x[q] = finish(x[q], c[q], row + q);
+                    if (OZ2_CRT_NT & 2) {
+                        typedef int i4v __attribute__((ext_vector_type(4)));
+                        __builtin_nontemporal_store(*reinterpret_cast<const i4v *>(x), reinterpret_cast<i4v *>(Cc + idx));
+                    } else {
+                        *reinterpret_cast<int4 *>(Cc + idx) = *reinterpret_cast<const int4 *>(x);
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < EPV; ++q)
+                        if (row + q < a.m && inside(row + q, col))
+                            Cc[idx + q] = finish(x[q], plain_ab || zero_beta ? E{} : Cc[idx + q], row + q);
+                }
+            }
+            wave_sync();
+        }
+    }
+}
+
+void crt_inverse_herk(const uint8_t *R, const Layout &L, const int16_t *sftA, const int16_t *sftB, const CrtParams &CP,
+                      OutType ot, const void *alpha, const void *beta, void *C, size_t ldc, bool upper, hipStream_t st) {
+    CrtArgs a{};
+    a.R = R;
+    a.planeR = L.planeR;
+    a.ldr = L.ldr;
+    a.sub = L.subR;
+    a.m = L.m;
+    a.n = L.n;
+    a.sftA = sftA;
+    a.sftB = sftB;
+    a.C = C;
+    a.ldc = ldc;
+    const bool f32 = ot == OutType::C32;
+    a.ar = f32 ? (double)*(const float *)alpha : *(const double *)alpha;
+    a.br = f32 ? (double)*(const float *)beta : *(const double *)beta;
+    // columns per block (a power of two up to 256): 2, the fastest or level with it at every size measured (CRT phase,
+    // N = 12, us, 1 / 2 / 4 / 8 columns: 1024^2 11.4 / 12.1 / 15.3 / 26.7, 2048^2 35-37 / 37-38 / 38 / 43-46, 4096^2
+    // 132-143 / 129-143 / 139-149 / 151-166, 8192^2 x 1024 511-539 / 496-529 / 508-524 / 505-523: DESIGN.md 9d);
+    // GEMMUL8_HERK_CRT_COLS (read once) forces another for A/B runs
+    static const unsigned cols_forced = [] {
+        const char *e = getenv("GEMMUL8_HERK_CRT_COLS");
+        const unsigned v = e ? (unsigned)atoi(e) : 0u;
+        return v >= 1 && v <= 256 && (v & (v - 1)) == 0 ? v : 0u;
+    }();
+    const unsigned cols = cols_forced ? cols_forced : 2u;
+    const size_t T = (L.m + 255) / 256, groups = (L.n + cols - 1) / cols;
+    const dim3 grid((unsigned)((T + 3) / 4), (unsigned)(groups < 65535 ? groups : 65535));
+    const int up = upper ? 1 : 0;
+    switch (CP.N) {
+#define OZ2_N(n) case n: if (f32) launch(crt_herk_kernel<3, true, n>, grid, dim3(256), st, a, up, cols); \
+                         else if (CP.numM1) launch(crt_herk_kernel<2, true, n>, grid, dim3(256), st, a, up, cols); \
+                         else launch(crt_herk_kernel<2, false, n>, grid, dim3(256), st, a, up, cols); break;
+        OZ2_N(2) OZ2_N(3) OZ2_N(4) OZ2_N(5) OZ2_N(6) OZ2_N(7) OZ2_N(8) OZ2_N(9) OZ2_N(10) OZ2_N(11)
+        OZ2_N(12) OZ2_N(13) OZ2_N(14) OZ2_N(15) OZ2_N(16) OZ2_N(17) OZ2_N(18) OZ2_N(19) OZ2_N(20)
+#undef OZ2_N
+    default: break;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Partial CRT sums of a moduli range and the CRT finished from summed partials: the north star's
 // multi-GPU form (BASELINE.json: "a single RCCL reduce of partial FP64 accumulators"), gemmul8/dist.py
 // gemm_moduli_reduce.  A rank that holds the residue planes of moduli [j0, j1) writes per element

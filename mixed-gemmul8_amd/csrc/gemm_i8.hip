@@ -1622,14 +1622,18 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_batched_onetile_kernel(Ba
 // b holds 16 b + 10 tiles and the ~32 tiles an XCD has in flight share about 4 row panels and 8 column panels,
 // as the gemm raster's 4 x 8 groups do.  uplo = upper is the same walk with (tm, tn) swapped: any (row panel,
 // column panel) pair is a valid tile of the shared plane.
+// Hermitian rank-k products (gemmul8_herk; SUB below): the same triangle of each of the three Karatsuba
+// sub-products P1 = Ar Br^T, P2 = Ai Bi^T, P3 = (Ar + Ai)(Br + Bi)^T of a modulus, B = A^H; the CRT needs Re and Im
+// on one triangle of C only, hence each P on that triangle only.  A unit is (plane y in [0, 3 N), raster position),
+// modulus y / 3, sub-product y mod 3; queues, XCD shares and claims run per plane y as above.
 struct SyrkArgs {
-    GemmArgs g;      // mtiles = ntiles = T, nplanes = N
+    GemmArgs g;      // mtiles = ntiles = T, nplanes = N (herk: 3 N, the Karatsuba sub-products counted)
     unsigned P;      // T (T + 1) / 2: tiles per plane
     unsigned upper;  // 1: the tile of raster position (tm, tn) is (tn, tm)
 };
 struct SyrkUnit {
-    unsigned j, tm, tn;
-    uint32_t offA, offB;  // byte offsets of the tile's first panels in plane j of A and of B
+    unsigned j, sb, tm, tn;  // modulus, Karatsuba sub-product (herk; else 0), tile
+    uint32_t offA, offB;     // byte offsets of the tile's first panels in plane j of A and of B
 };
 // raster position v in [0, P) -> (tm, tn), tn <= tm < T; a scalar loop over at most T / 4 bands and 4 columns
 __device__ __forceinline__ void syrk_raster(unsigned T, unsigned v, unsigned &tm, unsigned &tn) {
@@ -1655,16 +1659,19 @@ __device__ __forceinline__ void syrk_raster(unsigned T, unsigned v, unsigned &tm
     tn = r0 + c;
     tm = tn + v;
 }
-__device__ __forceinline__ SyrkUnit syrk_unit(const SyrkArgs &a, unsigned j, unsigned v) {
+// SUB (gemmul8_herk): y counts the Karatsuba sub-products, y = 3 j + s; sub-product s multiplies sub-block s of A's
+// plane j by sub-block s of B's ([re | im | re + im], strides subA / subB) into sub-plane s of residue plane j
+template <bool SUB> __device__ __forceinline__ SyrkUnit syrk_unit(const SyrkArgs &a, unsigned y, unsigned v) {
     SyrkUnit t;
     unsigned lo_r, lo_c;
     syrk_raster(a.g.mtiles, __builtin_amdgcn_readfirstlane(v), lo_r, lo_c);
     // block-uniform: SGPRs
-    t.j = __builtin_amdgcn_readfirstlane(j);
+    t.j = __builtin_amdgcn_readfirstlane(SUB ? y / 3 : y);
+    t.sb = SUB ? __builtin_amdgcn_readfirstlane(y - 3 * t.j) : 0;
     t.tm = __builtin_amdgcn_readfirstlane(a.upper ? lo_c : lo_r);
     t.tn = __builtin_amdgcn_readfirstlane(a.upper ? lo_r : lo_c);
-    t.offA = __builtin_amdgcn_readfirstlane((uint32_t)((size_t)t.tm * a.g.kstride * PANEL));
-    t.offB = __builtin_amdgcn_readfirstlane((uint32_t)((size_t)t.tn * a.g.kstride * PANEL));
+    t.offA = __builtin_amdgcn_readfirstlane((uint32_t)((SUB ? t.sb * a.g.subA : 0) + (size_t)t.tm * a.g.kstride * PANEL));
+    t.offB = __builtin_amdgcn_readfirstlane((uint32_t)((SUB ? t.sb * a.g.subB : 0) + (size_t)t.tn * a.g.kstride * PANEL));
     return t;
 }
 
@@ -1675,7 +1682,9 @@ __device__ __forceinline__ SyrkUnit syrk_unit(const SyrkArgs &a, unsigned j, uns
 // takes a contiguous share of the plane's raster (P / 8 tiles, the first P mod 8 queues one more).  A block's
 // first two units are static (its rank on the XCD, then that plus the XCD's block count), later ones claimed
 // from the queue head two units ahead.
-__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_kernel(SyrkArgs a) {
+// SUB: the same kernel over the 3 N sub-product planes of the Karatsuba geometry (gemm_i8_herk_kernel: plane y is
+// sub-product y mod 3 of modulus y / 3, whose constants it takes); one body, SUB = false folds to the real kernel.
+template <bool SUB> __device__ __forceinline__ void syrk_persistent(const SyrkArgs &a) {
     static_assert(OZ2_MFMA16, "per-group epilogue: 16x16x64 accumulator map");
     __shared__ __attribute__((aligned(1024))) int8_t smem[PLDS_BYTES + PARK_SPARE];
     const GemmArgs &g = a.g;
@@ -1693,7 +1702,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_kernel(SyrkArgs a) {
     const unsigned total = g.nplanes * tx;
     auto unit_at = [&](unsigned i) {
         const unsigned y = i / tx;
-        return syrk_unit(a, y, basex + (i - y * tx));
+        return syrk_unit<SUB>(a, y, basex + (i - y * tx));
     };
     auto claim = [&]() { return __hip_atomic_fetch_add(g.queue + xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
     auto to_unit = [&](unsigned pos) { return pos + 2 * nblk < total ? pos + 2 * nblk : NO_TILE; };
@@ -1830,8 +1839,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_kernel(SyrkArgs a) {
         }
         __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0), vmcnt untouched
         barrier();
-        uint8_t *out = static_cast<uint8_t *>(g.out) + (size_t)ct.j * g.planeOut + (size_t)ct.tn * 256 * g.ldo +
-                       (size_t)ct.tm * 256 + wr * 128;
+        uint8_t *out = static_cast<uint8_t *>(g.out) + (size_t)ct.j * g.planeOut + (SUB ? ct.sb * g.subOut : 0) +
+                       (size_t)ct.tn * 256 * g.ldo + (size_t)ct.tm * 256 + wr * 128;
 #pragma unroll
         for (int it = 0; it < PARK_STORES; ++it) {
             const int chunk = gtid + 256 * it;
@@ -1851,11 +1860,14 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_kernel(SyrkArgs a) {
     }
     if (wr == 0) barrier();  // group 0 passed one barrier fewer (group 1's initial one)
 }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_kernel(SyrkArgs a) { syrk_persistent<false>(a); }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_herk_kernel(SyrkArgs a) { syrk_persistent<true>(a); }
 
 // One-unit form (fewer than 6 k-steps, or fewer than 3 units per CU): grid (P, N), block x of plane y computes
 // the tile at raster position wgid(x) -- the gemm one-tile kernel's XCD remap, so the blocks an XCD receives are
 // a contiguous share of the plane's raster -- with the one-tile kernel's ring, ping-pong main loop and epilogue.
-__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_onetile_kernel(SyrkArgs a) {
+// SUB (gemm_i8_herk_onetile_kernel): grid (P, 3 N), blockIdx.y = 3 j + s.
+template <bool SUB> __device__ __forceinline__ void syrk_onetile(const SyrkArgs &a) {
     __shared__ __attribute__((aligned(1024))) int8_t smem[LDS_BYTES];
     const GemmArgs &g = a.g;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1864,7 +1876,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_onetile_kernel(SyrkA
     const unsigned nwg = gridDim.x, bid = blockIdx.x;
     const unsigned xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
     const unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const SyrkUnit u = syrk_unit(a, blockIdx.y, wgid);
+    const SyrkUnit u = syrk_unit<SUB>(a, blockIdx.y, wgid);
 
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
     const uint32_t lds_wave = lds_base + wave * 1024;
@@ -1919,8 +1931,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_onetile_kernel(SyrkA
     }
     if (wr == 0) barrier();
     barrier();  // all waves done with the ring before the epilogue reuses it
-    epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, 0, true, u.j);
+    epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, u.sb, true, u.j);
 }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_onetile_kernel(SyrkArgs a) { syrk_onetile<false>(a); }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_herk_onetile_kernel(SyrkArgs a) { syrk_onetile<true>(a); }
 
 // Exhaustive check of the two residue epilogues against exact arithmetic, every input and every
 // modulus: path 0 = biased (x in [-2^30, 2^30], the accumulator starting at bias_i), path 1 = signed
@@ -2288,12 +2302,14 @@ bool gemm_i8_batched(const int8_t *A8, const int8_t *B8, const Layout &L, unsign
     return true;
 }
 
-bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
-                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
-    const size_t T = L.mtiles, P = T * (T + 1) / 2, units = P * N;
+// sub: the Karatsuba geometry's 3 N sub-product planes (gemm_i8_herk), else the N planes of a real problem
+static bool syrk_products(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool sub, bool upper,
+                          uint8_t *R, const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
+    const unsigned planes = sub ? 3 * N : N;
+    const size_t T = L.mtiles, P = T * (T + 1) / 2, units = P * planes;
     const char *ff = getenv("GEMMUL8_FORCE_FLAT_DMA");
     // a square problem, buffer descriptors (planes < 4 GiB), the biased residue path, 32-bit unit counts
-    if (L.nsub != 1 || L.mtiles != L.ntiles || L.ksteps == 0 || L.k_pad > ((size_t)1 << 16) ||
+    if (L.nsub != (sub ? 3u : 1u) || L.mtiles != L.ntiles || L.ksteps == 0 || L.k_pad > ((size_t)1 << 16) ||
         L.planeA >= ((size_t)1 << 32) || L.planeB >= ((size_t)1 << 32) || (ff && atoi(ff)) || N == 0 || N > 65535 ||
         units == 0 || units > 0x0fffffffu)
         return false;
@@ -2305,11 +2321,14 @@ bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
     g.planeB = L.planeB;
     g.ksteps = g.kstride = (unsigned)L.ksteps;
     g.mtiles = g.ntiles = (unsigned)T;
-    g.nplanes = N;
+    g.nplanes = planes;
     g.out = R;
     g.planeOut = L.planeR;
     g.ldo = L.ldr;
-    g.nsub = 1;
+    g.nsub = sub ? 3 : 1;
+    g.subA = sub ? L.subA : 0;
+    g.subB = sub ? L.subB : 0;
+    g.subOut = sub ? L.subR : 0;
     g.biased = 1;
     for (int i = 0; i < OZ2_MAX_MODULI; ++i) {
         g.p[i] = MP.p[i];
@@ -2335,13 +2354,24 @@ bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
             return e ? (unsigned)atoi(e) : 0u;
         }();
         const unsigned grid = (unsigned)std::min<size_t>(units, std::min(ncu, grid_cap ? std::max(grid_cap, 8u) : ncu));
-        g_last_residue_kernel.store(8, std::memory_order_relaxed);
-        launch(gemm_i8_syrk_kernel, dim3(grid), dim3(NTHREADS), st, a);
+        g_last_residue_kernel.store(sub ? 10 : 8, std::memory_order_relaxed);
+        launch(sub ? gemm_i8_herk_kernel : gemm_i8_syrk_kernel, dim3(grid), dim3(NTHREADS), st, a);
     } else {
-        g_last_residue_kernel.store(9, std::memory_order_relaxed);
-        launch(gemm_i8_syrk_onetile_kernel, dim3((unsigned)P, N), dim3(NTHREADS), st, a);
+        g_last_residue_kernel.store(sub ? 11 : 9, std::memory_order_relaxed);
+        launch(sub ? gemm_i8_herk_onetile_kernel : gemm_i8_syrk_onetile_kernel, dim3((unsigned)P, planes),
+               dim3(NTHREADS), st, a);
     }
     return true;
+}
+
+bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
+    return syrk_products(A8, B8, L, N, false, upper, R, MP, st, queue, queue_zeroed);
+}
+
+bool gemm_i8_herk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
+    return syrk_products(A8, B8, L, N, true, upper, R, MP, st, queue, queue_zeroed);
 }
 
 }  // namespace oz2

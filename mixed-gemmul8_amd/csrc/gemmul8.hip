@@ -230,9 +230,11 @@ struct Views {
     int32_t *bound;
     uint32_t *queue;
 };
-static Views views(void *work, size_t m, size_t n, size_t k, unsigned N, bool cplx, unsigned slice_planes = 0) {
+// kara: make_layout's (-1 = kara_default for complex; 1 forces the Karatsuba geometry, gemmul8_herk)
+static Views views(void *work, size_t m, size_t n, size_t k, unsigned N, bool cplx, unsigned slice_planes = 0,
+                   int kara = -1) {
     Views v;
-    v.L = make_layout(m, n, k, N, cplx, slice_planes);
+    v.L = make_layout(m, n, k, N, cplx, slice_planes, kara);
     int8_t *base = static_cast<int8_t *>(work);
     v.A8 = base + v.L.offA;
     v.B8 = base + v.L.offB;
@@ -750,10 +752,98 @@ static int run_syrk(Call &c, bool upper, double *phase_ns) {
     return GEMMUL8_OK;
 }
 
+// ---------------- Hermitian rank-k update ----------------
+// c describes gemm(trans, opposite op, n, n, k, A, A) with complex operands (OperandDesc::conj makes the B-side
+// sub-blocks those of A^H).  The layout is always the Karatsuba one, whatever kara_default would choose for gemm:
+// the residues of Re and Im mod p are the same bits under either geometry (oz2_common.hpp), and only the three
+// sub-products are each needed on one triangle.  phase_split runs unchanged over that layout in both modes (the
+// accurate-mode bound product keeps its big-matrix geometry, phase_bound), so shifts and slices are gemm's by
+// construction.  The products are the triangle's tiles of the 3 N sub-product planes (gemm_i8_herk), or outside
+// their domain every tile of the same layout through gemm_i8; the CRT is the triangular one either way.
+static int run_herk(Call &c, bool upper, double *phase_ns) {
+    const Views v = views(c.work, c.n, c.n, c.k, c.N, true, 0, 1);
+    const Layout &L = v.L;
+    const bool capturing = is_capturing(c.st);
+    if (phase_ns && capturing)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    const bool want_events = phase_ns != nullptr && !capturing;
+    bool record;
+    timing::Rec rec{};
+    {
+        std::lock_guard<std::mutex> g(timing::mu);
+        record = want_events || (timing::enabled && !capturing);
+        if (record) rec = timing::acquire();
+    }
+    auto fail = [&]() {
+        if (record) {
+            std::lock_guard<std::mutex> g(timing::mu);
+            timing::pool.push_back(rec);
+        }
+        return GEMMUL8_E_HIP;
+    };
+    {
+        timing::Phase split(record, c.st, rec.start, nullptr);
+        phase_split(c, v, 0, c.N, false);
+        split.end();
+    }
+    if (!launch_ok()) return fail();
+    {
+        timing::Phase prod(record, c.st, rec.prod0, rec.prod1);
+        const ModParams MP = make_mod_params(c.N);
+        if (!gemm_i8_herk(v.A8, v.B8, L, c.N, upper, v.R, MP, c.st, v.queue, true))
+            gemm_i8(v.A8, v.B8, L, c.N, Epi::RESIDUE, v.R, nullptr, nullptr, MP, c.st, v.queue, true);
+        prod.end();
+    }
+    if (!launch_ok()) return fail();
+    {
+        timing::Phase crt(record, c.st, nullptr, rec.crt1);
+        crt_inverse_herk(v.R, L, v.sftA, v.sftB, make_crt_params(c.N, c.ot == OutType::C32), c.ot, c.alpha, c.beta, c.C,
+                         c.ldc, upper, c.st);
+        crt.end();
+    }
+    if (!launch_ok()) return fail();
+    if (want_events) {
+        float t[4];
+        timing::read(rec, t);
+        for (int i = 0; i < 4; ++i) phase_ns[i] = t[i] * 1e6;
+    }
+    if (record) {
+        std::lock_guard<std::mutex> g(timing::mu);
+        if (timing::enabled) timing::pending.push_back(rec);
+        else timing::pool.push_back(rec);
+    }
+    return GEMMUL8_OK;
+}
+
 }  // namespace oz2
 
 // =============================== C ABI ===================================
 extern "C" {
+
+size_t gemmul8_work_size_herk(size_t n, size_t k, unsigned num_moduli) {
+    return oz2::make_layout(n, n, k, num_moduli, true, 0, 1).total;
+}
+
+int gemmul8_herk(void *stream, int uplo, int trans, size_t n, size_t k, int type_a, int type_c, const void *alpha,
+                 const void *A, size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
+                 void *work, double *phase_ns) {
+    if (num_moduli < 2 || num_moduli > 20) return GEMMUL8_E_MODULI;
+    if (type_a < 0 || type_a > 3 || type_c < 0 || type_c > 3 || !oz2::dt_cplx(type_a) || !oz2::dt_cplx(type_c))
+        return GEMMUL8_E_TYPES;
+    if ((trans != GEMMUL8_OP_N && trans != GEMMUL8_OP_C) || (uplo != GEMMUL8_FILL_LOWER && uplo != GEMMUL8_FILL_UPPER))
+        return GEMMUL8_E_OP;
+    // alpha and beta are real (BLAS zherk / cherk); prepare only stores the pointers, crt_inverse_herk reads them
+    oz2::Call c{};
+    const int rc = oz2::prepare(stream, trans, trans == GEMMUL8_OP_N ? GEMMUL8_OP_C : GEMMUL8_OP_N, n, n, k, type_a,
+                                type_a, type_c, alpha, A, lda, A, lda, beta, C, ldc, num_moduli, fastmode, work,
+                                GEMMUL8_COMPLEX_KARATSUBA_MULT, c);
+    if (rc != GEMMUL8_OK) return rc;
+    if (phase_ns)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    if (n == 0) return GEMMUL8_OK;
+    oz2::clear_stale_error();
+    return oz2::run_herk(c, uplo == GEMMUL8_FILL_UPPER, phase_ns);
+}
 
 size_t gemmul8_work_size_syrk(size_t n, size_t k, unsigned num_moduli) {
     return oz2::make_layout(n, n, k, num_moduli, false).total;
@@ -1098,6 +1188,8 @@ const char *gemmul8_last_products_kernel(void) {
     case 7: return "gemm_i8_batched_onetile_kernel";
     case 8: return "gemm_i8_syrk_kernel";
     case 9: return "gemm_i8_syrk_onetile_kernel";
+    case 10: return "gemm_i8_herk_kernel";
+    case 11: return "gemm_i8_herk_onetile_kernel";
     default: return "none";
     }
 }

@@ -161,10 +161,16 @@ bool gemm_i8_batched(const int8_t *A8, const int8_t *B8, const Layout &L, unsign
 // false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB or forced flat DMA)
 bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
                   const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed);
+// The same triangle of the 3 N Karatsuba sub-product planes of a square complex problem (gemmul8_herk;
+// gemm_i8_herk_kernel / gemm_i8_herk_onetile_kernel): L is a Karatsuba layout (nsub = 3), sub-product s of modulus j
+// multiplies sub-block s of A8's plane j by sub-block s of B8's into sub-plane s of R's plane j.  Launch rule and
+// domain as gemm_i8_syrk, the units counted as 3 N P; false (nothing launched) outside the domain
+bool gemm_i8_herk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed);
 // the residue-product kernel of the last RESIDUE launch: 0 none yet, 1 one-tile (gemm_i8_kernel),
 // 2 persistent (gemm_i8_persistent_kernel), 3 k-chunked one-tile launches, 4 128 x 128 (gemm_i8_small_kernel),
 // 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit, 8 / 9 SYRK
-// persistent / one-unit; g_last_tail_small: its last planes ran as 128 x 128 tiles
+// persistent / one-unit, 10 / 11 HERK persistent / one-unit; g_last_tail_small: its last planes ran as 128 x 128 tiles
 extern std::atomic<int> g_last_residue_kernel;
 extern std::atomic<int> g_last_tail_small;
 // exhaustive exactness check of the residue epilogues (0 = biased, 1 = signed): mismatch count
@@ -186,6 +192,13 @@ void crt_inverse_batched(const uint8_t *R, const Layout &L, size_t batch, size_t
 // real CRT of one triangle of a square problem (gemmul8_syrk; crt_syrk_kernel, BLAS epilogue): column col's rows
 // >= col (upper: <= col) only; nothing outside the triangle is read from R or C or written
 void crt_inverse_syrk(const uint8_t *R, const Layout &L, const int16_t *sftA, const int16_t *sftB, const CrtParams &CP,
+                      OutType ot, const void *alpha, const void *beta, void *C, size_t ldc, bool upper, hipStream_t st);
+
+// complex CRT of one triangle of a square Karatsuba-layout problem (gemmul8_herk; crt_herk_kernel, BLAS epilogue):
+// alpha and beta point to one real host value of C's precision; column col's rows >= col (upper: <= col) only,
+// nothing outside the triangle is read from R or C or written; the diagonal's imaginary part is not read and is
+// written as +0.0
+void crt_inverse_herk(const uint8_t *R, const Layout &L, const int16_t *sftA, const int16_t *sftB, const CrtParams &CP,
                       OutType ot, const void *alpha, const void *beta, void *C, size_t ldc, bool upper, hipStream_t st);
 
 // partial CRT sums of moduli [j0, j1) into S ([2][n][lds]: C1 then C2) and the CRT finished from summed

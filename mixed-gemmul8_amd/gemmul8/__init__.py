@@ -64,6 +64,10 @@ def _load():
     lib.gemmul8_work_size_syrk.argtypes = [sz, sz, u]
     lib.gemmul8_syrk.restype = i
     lib.gemmul8_syrk.argtypes = [p, i, i, sz, sz, i, i, p, p, sz, p, p, sz, u, i, p, d]
+    lib.gemmul8_work_size_herk.restype = sz
+    lib.gemmul8_work_size_herk.argtypes = [sz, sz, u]
+    lib.gemmul8_herk.restype = i
+    lib.gemmul8_herk.argtypes = [p, i, i, sz, sz, i, i, p, p, sz, p, p, sz, u, i, p, d]
     lib.gemmul8_timing_enable.argtypes = [i]
     lib.gemmul8_timing_read.argtypes = [d, ctypes.POINTER(ctypes.c_int)]
     lib.gemmul8_layout.argtypes = [sz, sz, sz, u, i, ctypes.POINTER(ctypes.c_size_t)]
@@ -193,6 +197,26 @@ def syrk(uplo, trans, n, k, alpha, A, lda, beta, C, ldc, num_moduli, fastmode, w
     al, be = _scalar(alpha, C.dtype), _scalar(beta, C.dtype)
     pt = (ctypes.c_double * 4)() if phase_times else None
     _check(lib.gemmul8_syrk(_stream(stream), uplo, trans, n, k, ta, tc, al.ptr, A.data_ptr(), lda, be.ptr,
+                            C.data_ptr(), ldc, num_moduli, int(bool(fastmode)), work.data_ptr(), pt))
+    return list(pt) if phase_times else None
+
+
+def workSize_herk(n, k, num_moduli):
+    """Bytes of device workspace for herk: the Karatsuba geometry of the n x n x k complex problem."""
+    return int(lib.gemmul8_work_size_herk(n, k, num_moduli))
+
+
+def herk(uplo, trans, n, k, alpha, A, lda, beta, C, ldc, num_moduli, fastmode, work, stream=None, phase_times=False):
+    """The `uplo` triangle (FILL_LOWER / FILL_UPPER, diagonal included) of C = alpha*A*A^H + beta*C (trans = OP_N,
+    A n x k) or alpha*A^H*A + beta*C (OP_C, A k x n) on column-major complex device buffers, alpha and beta real;
+    the other triangle of C is neither read nor written.  Off the diagonal the triangle has the bits
+    gemm(trans, the opposite op, n, n, k, ..., A, A, ...) writes there; on the diagonal the imaginary part of C is
+    not read and is written as +0.0.  work holds workSize_herk bytes.  Returns the phase times like gemm."""
+    ta, tc = _DTYPE[A.dtype], _DTYPE[C.dtype]
+    real = torch.float64 if C.dtype == torch.complex128 else torch.float32
+    al, be = _scalar(alpha, real), _scalar(beta, real)
+    pt = (ctypes.c_double * 4)() if phase_times else None
+    _check(lib.gemmul8_herk(_stream(stream), uplo, trans, n, k, ta, tc, al.ptr, A.data_ptr(), lda, be.ptr,
                             C.data_ptr(), ldc, num_moduli, int(bool(fastmode)), work.data_ptr(), pt))
     return list(pt) if phase_times else None
 

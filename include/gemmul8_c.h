@@ -125,6 +125,35 @@ int gemmul8_herk(void *stream, int uplo, int trans, size_t n, size_t k, int type
                  const void *A, size_t lda, const void *beta, void *C, size_t ldc, unsigned num_moduli, int fastmode,
                  void *work, double *phase_ns);
 
+/* --- triangular matrix multiply --------------------------------------------------------------------
+ * side = GEMMUL8_SIDE_LEFT: C = alpha * op(A) * B with A m x m; GEMMUL8_SIDE_RIGHT: C = alpha * B * op(A) with A
+ * n x n; op = trans (GEMMUL8_OP_N / OP_T); B and C m x n; column-major.  A is triangular: only its `uplo` triangle is
+ * read, and with GEMMUL8_DIAG_UNIT not its diagonal either, which counts as exactly 1.0; the unreferenced elements
+ * never influence the result and may hold anything, NaN and Inf included.  There is no beta (the out-of-place form
+ * of rocBLAS / hipBLAS-v2 trmm): C is never read, the CRT runs with beta = 0 under BLAS epilogue semantics
+ * (gemmul8_set_epilogue does not apply).
+ * In place: C == B is allowed when ldc == ldb and type_c == type_b (BLAS trmm) -- split, products and CRT are
+ * ordered on the stream and B is split completely before the CRT writes C.  Any other overlap of C with A or B is
+ * undefined.
+ * C carries the bits gemmul8_gemm writes with beta = 0 for A's explicit dense form (zeros outside the triangle, ones
+ * on a unit diagonal): gemm(trans, N, m, n, m, A, B) on the left, gemm(N, trans, m, n, n, B, A) on the right, in
+ * fast and accurate mode and for ragged sizes.
+ * The split reads the triangle's half of A only, and the products run every tile over the k-steps its triangle
+ * leaves nonzero, (T + 1) / 2T of the full product's (T = tiles of 256 along A; "gemm_i8_trmm_kernel" /
+ * "gemm_i8_trmm_onetile_kernel").  Padded k beyond 2^16 runs gemmul8_gemm's products over all tiles.
+ * Real types only, in the combinations gemmul8_gemm accepts for type_a / type_b / type_c under
+ * GEMMUL8_REAL_DEFAULT; a complex type returns GEMMUL8_E_TYPES; GEMMUL8_OP_C or an unknown side / uplo / diag
+ * GEMMUL8_E_OP; moduli, size and leading-dimension checks are gemmul8_gemm's (lda >= m on the left, >= n on the
+ * right; ldb, ldc >= m); m == 0 or n == 0 returns GEMMUL8_OK; on any error nothing is enqueued.  phase_ns as
+ * gemmul8_gemm.  gemmul8_work_size_trmm(side, m, n, N) == gemmul8_work_size(m, n, side == LEFT ? m : n, N,
+ * GEMMUL8_REAL_DEFAULT). */
+enum { GEMMUL8_SIDE_LEFT = 0, GEMMUL8_SIDE_RIGHT = 1 };
+enum { GEMMUL8_DIAG_NON_UNIT = 0, GEMMUL8_DIAG_UNIT = 1 };
+size_t gemmul8_work_size_trmm(int side, size_t m, size_t n, unsigned num_moduli);
+int gemmul8_trmm(void *stream, int side, int uplo, int trans, int diag, size_t m, size_t n, int type_a, int type_b,
+                 int type_c, const void *alpha, const void *A, size_t lda, const void *B, size_t ldb, void *C,
+                 size_t ldc, unsigned num_moduli, int fastmode, void *work, double *phase_ns);
+
 /* --- phase entry points (multi-GPU sharding, gemmul8/dist.py) ------------------------------------
  * gemmul8_gemm == gemmul8_split(0, N) + gemmul8_products(0, N) + gemmul8_recombine, on one stream.
  * Splitting the moduli range lets a rank produce only the residue planes [mod_begin, mod_end)
@@ -256,8 +285,9 @@ int gemmul8_get_epilogue(void);
 /* Name of the residue-product kernel the last products launch of this process took
  * ("gemm_i8_persistent_pg_kernel", "gemm_i8_persistent_kernel", "gemm_i8_kernel", "gemm_i8_small_kernel",
  * "gemm_i8_kernel (k-chunked)", "gemm_i8_batched_kernel", "gemm_i8_batched_onetile_kernel", "gemm_i8_syrk_kernel",
- * "gemm_i8_syrk_onetile_kernel", "gemm_i8_herk_kernel", "gemm_i8_herk_onetile_kernel" or "none"; a gemmul8_syrk or
- * gemmul8_herk call outside the triangular kernels' domain reports the gemm kernel that ran all tiles). */
+ * "gemm_i8_syrk_onetile_kernel", "gemm_i8_herk_kernel", "gemm_i8_herk_onetile_kernel", "gemm_i8_trmm_kernel",
+ * "gemm_i8_trmm_onetile_kernel" or "none"; a gemmul8_syrk, gemmul8_herk or gemmul8_trmm call outside its own
+ * kernels' domain reports the gemm kernel that ran all tiles). */
 const char *gemmul8_last_products_kernel(void);
 
 /* --- bench / test harness (not part of the emulation path) ------------------------------------ */

@@ -1936,6 +1936,324 @@ template <bool SUB> __device__ __forceinline__ void syrk_onetile(const SyrkArgs 
 __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_syrk_onetile_kernel(SyrkArgs a) { syrk_onetile<false>(a); }
 __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_herk_onetile_kernel(SyrkArgs a) { syrk_onetile<true>(a); }
 
+// ---------------------------------------------------------------------------------------------
+// Triangular matrix multiply residue products (gemmul8_trmm): every tile of the full m_pad x n_pad residue
+// planes, but each over its own k-range.  One operand's slices are those of a triangular matrix (split.hip encodes
+// exact zeros outside the triangle), so the tile whose index along the clipped dimension is t (tm: the triangle is
+// the row operand, side left; tn: the column operand, side right) multiplies zeros outside
+//     k <= t:  k-steps [0, min(K, 4 (t + 1)))        k >= t:  k-steps [4 t, K)
+// (a tile spans 4 k-steps of 64).  A unit is (modulus j, tile) with its own first step and length; its panels start
+// kbeg panels into the tile's panel rows.  Summed over t this is (T + 1) / 2T of the full product's steps.
+// Order: a unit costs its length, up to T times the shortest, so every queue hands out long units first and the
+// launch ends on short ones.  Clip rank c = 0 is the longest tile index (t = Tc - 1 - c for k <= t, t = c for
+// k >= t); ranks go in bands of 4, a band walked along the other dimension rank-fastest, so consecutive raster
+// positions share the band's 4 clipped panels and one panel of the other operand.  The persistent kernel's XCD x
+// takes a contiguous eighth of every (band, modulus) and walks   band (long to short) > modulus > its eighth:
+// each XCD holds the same share of every length (balanced queues), the whole launch runs one band of all the moduli
+// before the next shorter one, and the ~32 units an XCD has in flight come from one or two moduli's eighths
+// (4 clipped panels x a few of the other operand's each).
+struct TrmmArgs {
+    GemmArgs g;       // mtiles, ntiles, nplanes = N
+    unsigned Tc, To;  // tiles along the clipped dimension and along the other one
+    unsigned on_n;    // 1: the clipped tile index is tn, else tm
+    unsigned hi;      // 1: k >= t, else k <= t
+    unsigned kmin;    // least unit length in k-steps (<= K): shorter units are widened into the encoded zeros
+};
+struct TrmmUnit {
+    unsigned j, tm, tn, klen;  // modulus, tile, k-steps
+    uint32_t offA, offB;       // byte offsets of the unit's first panels in plane j of A and of B
+};
+// band b (4 b <= clip rank < 4 b + h), position pos in [0, h To) within it, modulus j
+__device__ __forceinline__ TrmmUnit trmm_unit(const TrmmArgs &a, unsigned j, unsigned b, unsigned h, unsigned pos) {
+    TrmmUnit u;
+    pos = __builtin_amdgcn_readfirstlane(pos);
+    const unsigned o = pos / h, c = 4 * b + (pos - o * h);
+    const unsigned t = a.hi ? c : a.Tc - 1 - c, K = a.g.ksteps;
+    unsigned kbeg = a.hi ? 4 * t : 0u, kend = a.hi ? K : min(K, 4 * (t + 1));
+    if (kend - kbeg < a.kmin) {  // kmin <= K (host)
+        if (a.hi) kbeg = K - a.kmin;
+        else kend = a.kmin;
+    }
+    u.j = __builtin_amdgcn_readfirstlane(j);
+    u.tm = __builtin_amdgcn_readfirstlane(a.on_n ? o : t);
+    u.tn = __builtin_amdgcn_readfirstlane(a.on_n ? t : o);
+    u.klen = __builtin_amdgcn_readfirstlane(kend - kbeg);
+    u.offA = __builtin_amdgcn_readfirstlane((uint32_t)(((size_t)u.tm * a.g.kstride + kbeg) * PANEL));
+    u.offB = __builtin_amdgcn_readfirstlane((uint32_t)(((size_t)u.tn * a.g.kstride + kbeg) * PANEL));
+    return u;
+}
+// share x of 8 of n items: first item and count (the first n mod 8 shares hold one more)
+__device__ __forceinline__ void share8(unsigned n, unsigned x, unsigned &base, unsigned &cnt) {
+    const unsigned q8 = n >> 3, r8 = n & 7;
+    cnt = q8 + (x < r8 ? 1u : 0u);
+    base = x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8;
+}
+
+// Persistent form (K >= 6, every unit at least 6 steps: kmin): syrk_persistent's pipeline -- 4-slot LDS-DMA ring
+// three k-steps ahead across unit boundaries, the two wave groups one barrier apart, each group parking and storing
+// its own 128 rows, first MFMA from the bias splat, biased f64 residues, non-temporal stores -- with the unit's
+// length a per-unit scalar: the ring's cursor jumps after staging the CURRENT unit's last step (klen - 4, at or
+// after step 2, where the next unit is known: hence 6) to the NEXT unit's first panel (its kbeg is in offA / offB),
+// and the drain of the block's last unit counts the current unit's steps.  The three steps staged after the jump
+// are the next unit's prologue whatever its length (>= 6 > 3).
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kernel(TrmmArgs a) {
+    static_assert(OZ2_MFMA16, "per-group epilogue: 16x16x64 accumulator map");
+    __shared__ __attribute__((aligned(1024))) int8_t smem[PLDS_BYTES + PARK_SPARE];
+    const GemmArgs &g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 2, wc = wave & 3;
+    uint32_t *const spare = reinterpret_cast<uint32_t *>(smem + PLDS_BYTES);
+    if (wr == 1) __builtin_amdgcn_s_setprio(1);
+
+    const unsigned G = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
+    const unsigned nblk = (G >> 3) + (xcd < (G & 7) ? 1u : 0u);
+    // this XCD's queue: nfull bands of 4 ranks (txF units per modulus each, from position baseF), then the last
+    // band of hl < 4 ranks (txL, baseL)
+    const unsigned nfull = a.Tc >> 2, hl = a.Tc & 3;
+    unsigned baseF, txF, baseL, txL;
+    share8(4 * a.To, xcd, baseF, txF);
+    share8(hl * a.To, xcd, baseL, txL);
+    const unsigned perF = g.nplanes * txF, nF = nfull * perF;
+    const unsigned total = nF + g.nplanes * txL;
+    auto unit_at = [&](unsigned i) {
+        if (i < nF) {
+            const unsigned b = i / perF, r = i - b * perF, y = r / txF;
+            return trmm_unit(a, y, b, 4, baseF + (r - y * txF));
+        }
+        const unsigned r = i - nF, y = r / txL;
+        return trmm_unit(a, y, nfull, hl, baseL + (r - y * txL));
+    };
+    auto claim = [&]() { return __hip_atomic_fetch_add(g.queue + xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto to_unit = [&](unsigned pos) { return pos + 2 * nblk < total ? pos + 2 * nblk : NO_TILE; };
+    const unsigned ccur = (bid >> 3) < total ? (bid >> 3) : NO_TILE;
+    if (ccur == NO_TILE) return;  // block-uniform, before any barrier
+    if (tid == 0) {
+        const unsigned second = nblk + (bid >> 3);
+        spare[0] = second < total ? second : NO_TILE;
+    }
+
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
+    const uint32_t lds_wave = lds_base + wave * 1024;
+    const uint32_t lane_off = wave * 1024 + lane * 16;
+    auto rsrcA = [&](const TrmmUnit &t) { return make_rsrc(g.A + (size_t)t.j * g.planeA, (uint32_t)g.planeA); };
+    auto rsrcB = [&](const TrmmUnit &t) { return make_rsrc(g.B + (size_t)t.j * g.planeB, (uint32_t)g.planeB); };
+    auto lo_of = [&](unsigned step) { return lds_wave + (step & (PSTAGES - 1)) * SLOT; };
+    auto rd_of = [&](unsigned step) { return smem + (step & (PSTAGES - 1)) * SLOT; };
+
+    TrmmUnit ct = unit_at(ccur);
+    v4si rA = rsrcA(ct), rB = rsrcB(ct);
+    constexpr unsigned D = PSTAGES - 1;
+    for (unsigned s0 = 0; s0 < D; ++s0) {
+        const uint32_t lo = lo_of(s0);
+        bglds16(rA, ct.offA + s0 * PANEL + lane_off, lo);
+        bglds16(rA, ct.offA + s0 * PANEL + lane_off + 8192, lo + 8192);
+        bglds16(rB, ct.offB + s0 * PANEL + lane_off, lo + PANEL);
+        bglds16(rB, ct.offB + s0 * PANEL + lane_off + 8192, lo + PANEL + 8192);
+    }
+    wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();  // step 0 landed (and the second unit's LDS write)
+    barrier();
+
+    unsigned s = 0;
+    unsigned cnext = __builtin_amdgcn_readfirstlane(spare[0]);
+    uint32_t da = ct.offA + D * PANEL, db = ct.offB + D * PANEL;
+    Frags f;
+    AccTile acc[ACC_I][ACC_J];
+    unsigned pos = 0;  // thread 0: the queue position claimed for the unit after next
+    bool claimed = false;
+    if (wr == 1) barrier();  // group 1 falls one barrier behind, for the whole launch
+    for (unsigned r = 0;; ++r) {
+        const v4i bias = v4i{} + g.bias[ct.j];
+        const unsigned K = ct.klen;  // this unit's steps, >= 6
+        unsigned k = 0;
+        uint32_t na = 0, nb = 0;
+        v4si nrA = rA, nrB = rB;
+        auto step = [&](auto wait, auto first, auto mid) {
+            read_frags(f, rd_of(s), wr, wc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t lo = lo_of(s + D);
+            bglds16(rA, da + lane_off, lo);
+            bglds16(rA, da + lane_off + 8192, lo + 8192);
+            bglds16(rB, db + lane_off, lo + PANEL);
+            bglds16(rB, db + lane_off + 8192, lo + PANEL + 8192);
+            const bool jump = k + D + 1 == K;  // this unit's last step staged: on to the next unit's first panels
+            da = jump ? na : da + PANEL;
+            db = jump ? nb : db + PANEL;
+            if (jump) {  // block-uniform
+                rA = nrA;
+                rB = nrB;
+            }
+            wait();
+            barrier();
+            if constexpr (decltype(first)::value) mfma_step_first(acc, f, bias);
+            else mfma_step<1>(acc, f);
+            mid();
+            barrier();
+        };
+        auto none = [] {};
+        // steps 0 and 1: from the second unit on, the previous unit's 8 residue stores are younger than the DMA
+        auto wait01 = [&] {
+            if (r > 0) wait_vm_lgkm0<GLDS_PER_STEP *(D - 1) + PARK_STORES>();
+            else wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+        };
+        step(wait01, std::true_type{}, [&] {
+            if (claimed) {  // group 0's MFMA interval: group 1 has read its parked residues back
+                unsigned p2 = pos;
+                asm volatile("" : "+v"(p2));
+                spare[0] = to_unit(p2);
+                __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0)
+            }
+        });
+        ++k, ++s;
+        step(wait01, std::false_type{}, none);
+        ++k, ++s;
+        if (r > 0) cnext = __builtin_amdgcn_readfirstlane(spare[0]);  // published by thread 0 two barriers ago
+        TrmmUnit nt = ct;
+        if (cnext != NO_TILE) {
+            nt = unit_at(cnext);
+            na = nt.offA;
+            nb = nt.offB;
+            nrA = rsrcA(nt);
+            nrB = rsrcB(nt);
+        }
+        const unsigned kend = cnext != NO_TILE ? K : K - D;
+        for (; k < kend; ++k, ++s) step([] { wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>(); }, std::false_type{}, none);
+        for (; k < K; ++k, ++s) {  // drain of the block's last unit
+            read_frags(f, rd_of(s), wr, wc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            wait_steps_lgkm0<GLDS_PER_STEP>(k + 2 < K ? (int)(K - k - 2) : 0);
+            barrier();
+            mfma_step<1>(acc, f);
+            barrier();
+        }
+
+        // ---- this group's epilogue: park interval, then store interval (the per-group kernel's layout) ----
+        claimed = tid == 0 && cnext != NO_TILE;
+        if (claimed) pos = claim();
+        int etid = tid;
+        asm volatile("" : "+v"(etid));
+        const int elane = etid & 63, gtid = etid & 255;
+        const int p = g.p[ct.j];
+        uint32_t *const park = wr == 0 ? reinterpret_cast<uint32_t *>(rd_of(s - 1)) : spare;
+        auto park_all = [&](auto &&res) {
+            const int t7 = elane & 7;
+            uint32_t *const pb = park + (wc * 64 + (elane & 15)) * 32 + (elane >> 4);
+#pragma unroll
+            for (int i = 0; i < ACC_I; ++i) {
+                uint32_t *const pi = pb + 4 * (i ^ t7);
+#pragma unroll
+                for (int jj = 0; jj < ACC_J; ++jj) {
+                    uint32_t w = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w |= res(acc[i][jj][e]) << (8 * e);
+                    pi[jj * 16 * 32] = w;
+                }
+            }
+        };
+        if (p == 256) {
+            park_all([&](int x) { return (uint32_t)x & 0xffu; });
+        } else {
+            const double invp = g.invp[ct.j], pneg = -(double)p;
+            const double cneg = __builtin_fma(-0x1p52, invp, 0x1p-8);
+            park_all([&](int x) { return residue_biased_f64((uint32_t)x, invp, cneg, pneg); });
+        }
+        __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0), vmcnt untouched
+        barrier();
+        uint8_t *out = static_cast<uint8_t *>(g.out) + (size_t)ct.j * g.planeOut + (size_t)ct.tn * 256 * g.ldo +
+                       (size_t)ct.tm * 256 + wr * 128;
+#pragma unroll
+        for (int it = 0; it < PARK_STORES; ++it) {
+            const int chunk = gtid + 256 * it;
+            const int col = chunk >> 3, c = chunk & 7;
+            const uint4 v = *reinterpret_cast<const uint4 *>(park + col * 32 + ((c ^ (col & 7)) << 2));
+            typedef unsigned u4v __attribute__((ext_vector_type(4)));
+            const u4v val = u4v{v.x, v.y, v.z, v.w};
+            u4v *dst = reinterpret_cast<u4v *>(out + (size_t)col * g.ldo + 16 * c);
+            if (OZ2_RES_NTS) __builtin_nontemporal_store(val, dst);
+            else *dst = val;
+        }
+        if (claimed) asm volatile("" ::"v"(pos));  // the claim returned (older than the 8 stores: vmcnt(8))
+        __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // park reads done
+        barrier();
+        if (cnext == NO_TILE) break;
+        ct = nt;
+    }
+    if (wr == 0) barrier();  // group 0 passed one barrier fewer (group 1's initial one)
+}
+
+// One-unit form (K < 6, or fewer than 3 units per CU): grid (Tc To, N), block x of modulus y computes the unit at
+// raster position wgid(x) of the long-first raster above (the gemm one-tile kernel's XCD remap: an XCD's blocks are
+// a contiguous share, dispatched in order) with the one-tile kernel's ring, ping-pong loop and epilogue over the
+// unit's own steps.
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_onetile_kernel(TrmmArgs a) {
+    __shared__ __attribute__((aligned(1024))) int8_t smem[LDS_BYTES];
+    const GemmArgs &g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 2, wc = wave & 3;
+    const unsigned nwg = gridDim.x, bid = blockIdx.x;
+    unsigned base, cnt;
+    share8(nwg, bid & 7, base, cnt);
+    const unsigned wgid = __builtin_amdgcn_readfirstlane(base + (bid >> 3));
+    const unsigned b = wgid / (4 * a.To), h = min(4u, a.Tc - 4 * b);  // every band before the last is full
+    const TrmmUnit u = trmm_unit(a, blockIdx.y, b, h, wgid - b * 4 * a.To);
+
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
+    const uint32_t lds_wave = lds_base + wave * 1024;
+    const v4si rA = make_rsrc(g.A + (size_t)u.j * g.planeA, (uint32_t)g.planeA);
+    const v4si rB = make_rsrc(g.B + (size_t)u.j * g.planeB, (uint32_t)g.planeB);
+    const uint32_t oA = u.offA + wave * 1024 + lane * 16, oB = u.offB + wave * 1024 + lane * 16;
+    auto stage = [&](unsigned ks, unsigned slot) {
+        const uint32_t g32 = ks * (uint32_t)PANEL, lo = lds_wave + slot * SLOT;
+        bglds16(rA, oA + g32, lo);
+        bglds16(rA, oA + g32 + 8192, lo + 8192);
+        bglds16(rB, oB + g32, lo + PANEL);
+        bglds16(rB, oB + g32 + 8192, lo + PANEL + 8192);
+    };
+
+    AccTile acc[ACC_I][ACC_J];
+    const int acc0 = g.bias[u.j];
+#pragma unroll
+    for (int i = 0; i < ACC_I; ++i)
+#pragma unroll
+        for (int jj = 0; jj < ACC_J; ++jj) acc[i][jj] = AccTile{} + acc0;
+
+    const unsigned K = u.klen;  // >= 1: the unit's own steps, counted from its first panel
+    constexpr unsigned D = STAGES - 1;
+    // barrier accounting as gemm_i8_kernel: 1 + 2K + 1 per group before the epilogue
+    for (unsigned s0 = 0; s0 < D; ++s0)
+        if (s0 < K) stage(s0, s0);
+    if (K >= D) wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+    else wait_steps_lgkm0<GLDS_PER_STEP>((int)K - 1);
+    barrier();
+    if (wr == 1) barrier();
+    Frags f;
+    unsigned slot_cur = 0, slot_issue = D % STAGES, t = 0;
+    for (; t + D < K; ++t) {  // steady state
+        read_frags(f, smem + slot_cur * SLOT, wr, wc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        stage(t + D, slot_issue);
+        wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+        barrier();
+        mfma_step(acc, f);
+        barrier();
+        slot_cur = slot_cur == STAGES - 1 ? 0 : slot_cur + 1;
+        slot_issue = slot_issue == STAGES - 1 ? 0 : slot_issue + 1;
+    }
+    for (; t < K; ++t) {  // drain
+        read_frags(f, smem + slot_cur * SLOT, wr, wc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        wait_steps_lgkm0<GLDS_PER_STEP>(t + 2 < K ? (int)(K - t - 2) : 0);
+        barrier();
+        mfma_step(acc, f);
+        barrier();
+        slot_cur = slot_cur == STAGES - 1 ? 0 : slot_cur + 1;
+    }
+    if (wr == 0) barrier();
+    barrier();  // all waves done with the ring before the epilogue reuses it
+    epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, 0, true, u.j);
+}
+
 // Exhaustive check of the two residue epilogues against exact arithmetic, every input and every
 // modulus: path 0 = biased (x in [-2^30, 2^30], the accumulator starting at bias_i), path 1 = signed
 // Barrett (every int32, conv_32i_2_8u.hpp:7-56).  Counts mismatches into *count.
@@ -2372,6 +2690,67 @@ bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
 bool gemm_i8_herk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
                   const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
     return syrk_products(A8, B8, L, N, true, upper, R, MP, st, queue, queue_zeroed);
+}
+
+bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, KClip clip, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
+    const size_t P = L.mtiles * L.ntiles, units = P * N;
+    const char *ff = getenv("GEMMUL8_FORCE_FLAT_DMA");
+    // buffer descriptors (planes < 4 GiB), the biased residue path, one sub-product, 32-bit unit counts
+    if (L.nsub != 1 || L.ksteps == 0 || L.k_pad > ((size_t)1 << 16) || L.planeA >= ((size_t)1 << 32) ||
+        L.planeB >= ((size_t)1 << 32) || (ff && atoi(ff)) || N == 0 || N > 65535 || units == 0 || units > 0x0fffffffu)
+        return false;
+    TrmmArgs a{};
+    GemmArgs &g = a.g;
+    g.A = A8;
+    g.B = B8;
+    g.planeA = L.planeA;
+    g.planeB = L.planeB;
+    g.ksteps = g.kstride = (unsigned)L.ksteps;
+    g.mtiles = (unsigned)L.mtiles;
+    g.ntiles = (unsigned)L.ntiles;
+    g.nplanes = N;
+    g.out = R;
+    g.planeOut = L.planeR;
+    g.ldo = L.ldr;
+    g.nsub = 1;
+    g.biased = 1;
+    for (int i = 0; i < OZ2_MAX_MODULI; ++i) {
+        g.p[i] = MP.p[i];
+        g.barrett[i] = MP.barrett[i];
+        const uint32_t p = MP.p[i] > 0 ? (uint32_t)MP.p[i] : 256u;
+        g.minv[i] = (uint32_t)((((uint64_t)1) << 32) / p);
+        g.bias[i] = (int)(((((uint64_t)1) << 30) + p - 1) / p * p);
+        g.invp[i] = 1.0 / (double)p;
+    }
+    g.queue = queue;
+    a.on_n = clip.on_n ? 1u : 0u;
+    a.hi = clip.hi ? 1u : 0u;
+    a.Tc = clip.on_n ? g.ntiles : g.mtiles;
+    a.To = clip.on_n ? g.mtiles : g.ntiles;
+    g_last_tail_small.store(0, std::memory_order_relaxed);
+    // gemm's rule over the units: persistent from 3 units per CU and 6 k-steps (GEMMUL8_PERSISTENT=0 / 1: never /
+    // wherever the kernel applies), the one-unit launch below that
+    const unsigned ncu = device_cu_count();
+    const int pmode = persistent_mode();
+    // (at least 8 units, hence 8 blocks: every XCD's queue is served by blocks of that XCD only)
+    if (queue && g.ksteps >= 6 && units >= 8 && pmode != 0 && (pmode == 1 || units >= 3 * (size_t)ncu)) {
+        if (!queue_zeroed) zero_i32(reinterpret_cast<int32_t *>(queue), 8, st);
+        // GEMMUL8_PERSISTENT_GRID caps the grid as it does for gemm_i8, at no fewer than 8 blocks (one per queue)
+        static const unsigned grid_cap = [] {
+            const char *e = getenv("GEMMUL8_PERSISTENT_GRID");
+            return e ? (unsigned)atoi(e) : 0u;
+        }();
+        const unsigned grid = (unsigned)std::min<size_t>(units, std::min(ncu, grid_cap ? std::max(grid_cap, 8u) : ncu));
+        a.kmin = 6;
+        g_last_residue_kernel.store(12, std::memory_order_relaxed);
+        launch(gemm_i8_trmm_kernel, dim3(grid), dim3(NTHREADS), st, a);
+    } else {
+        a.kmin = 1;
+        g_last_residue_kernel.store(13, std::memory_order_relaxed);
+        launch(gemm_i8_trmm_onetile_kernel, dim3((unsigned)P, N), dim3(NTHREADS), st, a);
+    }
+    return true;
 }
 
 }  // namespace oz2

@@ -815,10 +815,112 @@ static int run_herk(Call &c, bool upper, double *phase_ns) {
     return GEMMUL8_OK;
 }
 
+// ---------------- triangular matrix multiply ----------------
+// c describes the equivalent gemm -- side left gemm(trans, N, m, n, m, A, B), side right gemm(N, trans, m, n, n, B, A)
+// -- with the triangle on A's descriptor (OperandDesc::tri / unit): the split encodes the triangular operand's
+// explicit dense form (zeros outside, ones on a unit diagonal) without reading the rest, the dense operand as gemm
+// does.  The pair / fused / one-read launchers refuse a triangular operand, so phase_split falls through to its
+// single-operand launches; everything runs on the caller's stream, and every operand is split before the CRT
+// writes C, which is what allows C == B.  The products are the k-clipped units (gemm_i8_trmm), or outside their
+// domain every tile over all of k through gemm_i8 (the zeros are encoded); the CRT is gemm's with beta = 0.
+static int run_trmm(Call &c, KClip clip, double *phase_ns) {
+    const Views v = views(c.work, c.m, c.n, c.k, c.N, false);
+    const Layout &L = v.L;
+    const bool capturing = is_capturing(c.st);
+    if (phase_ns && capturing)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    const bool want_events = phase_ns != nullptr && !capturing;
+    bool record;
+    timing::Rec rec{};
+    {
+        std::lock_guard<std::mutex> g(timing::mu);
+        record = want_events || (timing::enabled && !capturing);
+        if (record) rec = timing::acquire();
+    }
+    auto fail = [&]() {
+        if (record) {
+            std::lock_guard<std::mutex> g(timing::mu);
+            timing::pool.push_back(rec);
+        }
+        return GEMMUL8_E_HIP;
+    };
+    {
+        timing::Phase split(record, c.st, rec.start, nullptr);
+        phase_split(c, v, 0, c.N, false);
+        split.end();
+    }
+    if (!launch_ok()) return fail();
+    {
+        timing::Phase prod(record, c.st, rec.prod0, rec.prod1);
+        const ModParams MP = make_mod_params(c.N);
+        if (!gemm_i8_trmm(v.A8, v.B8, L, c.N, clip, v.R, MP, c.st, v.queue, true))
+            gemm_i8(v.A8, v.B8, L, c.N, Epi::RESIDUE, v.R, nullptr, nullptr, MP, c.st, v.queue, true);
+        prod.end();
+    }
+    if (!launch_ok()) return fail();
+    {
+        timing::Phase crt(record, c.st, nullptr, rec.crt1);
+        crt_inverse(v.R, L, v.sftA, v.sftB, make_crt_params(c.N, c.ot == OutType::F32), c.ot, c.alpha, c.beta, c.C,
+                    c.ldc, c.st, 0);
+        crt.end();
+    }
+    if (!launch_ok()) return fail();
+    if (want_events) {
+        float t[4];
+        timing::read(rec, t);
+        for (int i = 0; i < 4; ++i) phase_ns[i] = t[i] * 1e6;
+    }
+    if (record) {
+        std::lock_guard<std::mutex> g(timing::mu);
+        if (timing::enabled) timing::pending.push_back(rec);
+        else timing::pool.push_back(rec);
+    }
+    return GEMMUL8_OK;
+}
+
 }  // namespace oz2
 
 // =============================== C ABI ===================================
 extern "C" {
+
+size_t gemmul8_work_size_trmm(int side, size_t m, size_t n, unsigned num_moduli) {
+    return oz2::make_layout(m, n, side == GEMMUL8_SIDE_LEFT ? m : n, num_moduli, false).total;
+}
+
+int gemmul8_trmm(void *stream, int side, int uplo, int trans, int diag, size_t m, size_t n, int type_a, int type_b,
+                 int type_c, const void *alpha, const void *A, size_t lda, const void *B, size_t ldb, void *C,
+                 size_t ldc, unsigned num_moduli, int fastmode, void *work, double *phase_ns) {
+    if (num_moduli < 2 || num_moduli > 20) return GEMMUL8_E_MODULI;
+    if (type_a < 0 || type_a > 3 || type_b < 0 || type_b > 3 || type_c < 0 || type_c > 3 || oz2::dt_cplx(type_a) ||
+        oz2::dt_cplx(type_b) || oz2::dt_cplx(type_c))
+        return GEMMUL8_E_TYPES;
+    if ((trans != GEMMUL8_OP_N && trans != GEMMUL8_OP_T) || (side != GEMMUL8_SIDE_LEFT && side != GEMMUL8_SIDE_RIGHT) ||
+        (uplo != GEMMUL8_FILL_LOWER && uplo != GEMMUL8_FILL_UPPER) ||
+        (diag != GEMMUL8_DIAG_NON_UNIT && diag != GEMMUL8_DIAG_UNIT))
+        return GEMMUL8_E_OP;
+    static const double zero_d = 0.0;
+    static const float zero_f = 0.0f;
+    const void *beta = type_c == GEMMUL8_R_64F ? static_cast<const void *>(&zero_d) : &zero_f;
+    const bool right = side == GEMMUL8_SIDE_RIGHT;
+    oz2::Call c{};
+    const int rc = right ? oz2::prepare(stream, GEMMUL8_OP_N, trans, m, n, n, type_b, type_a, type_c, alpha, B, ldb, A,
+                                        lda, beta, C, ldc, num_moduli, fastmode, work, GEMMUL8_REAL_DEFAULT, c)
+                         : oz2::prepare(stream, trans, GEMMUL8_OP_N, m, n, m, type_a, type_b, type_c, alpha, A, lda, B,
+                                        ldb, beta, C, ldc, num_moduli, fastmode, work, GEMMUL8_REAL_DEFAULT, c);
+    if (rc != GEMMUL8_OK) return rc;
+    if (phase_ns)
+        for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
+    if (m == 0 || n == 0) return GEMMUL8_OK;
+    // Along k, row i of a lower triangular op(A) keeps k <= i and its column j keeps k >= j (upper: the reverse).
+    // "Effective lower": the stored triangle, flipped by a transpose.  The triangular operand's vectors are the rows
+    // on the left and the columns on the right, and the products' k-range follows the same relation per tile.
+    const bool eff_lower = (uplo == GEMMUL8_FILL_LOWER) != (trans != GEMMUL8_OP_N);
+    oz2::OperandDesc &T = right ? c.B : c.A;
+    T.tri = eff_lower != right ? oz2::TRI_LE : oz2::TRI_GE;
+    T.unit = diag == GEMMUL8_DIAG_UNIT;
+    oz2::clear_stale_error();
+    return oz2::run_trmm(c, oz2::KClip{right, T.tri == oz2::TRI_GE}, phase_ns);
+}
 
 size_t gemmul8_work_size_herk(size_t n, size_t k, unsigned num_moduli) {
     return oz2::make_layout(n, n, k, num_moduli, true, 0, 1).total;
@@ -1190,6 +1292,8 @@ const char *gemmul8_last_products_kernel(void) {
     case 9: return "gemm_i8_syrk_onetile_kernel";
     case 10: return "gemm_i8_herk_kernel";
     case 11: return "gemm_i8_herk_onetile_kernel";
+    case 12: return "gemm_i8_trmm_kernel";
+    case 13: return "gemm_i8_trmm_onetile_kernel";
     default: return "none";
     }
 }

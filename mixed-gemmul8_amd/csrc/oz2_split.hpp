@@ -59,6 +59,8 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t 
     }
 }
 
+enum : int { TRI_NONE = 0, TRI_LE = 1, TRI_GE = 2, TRI_UNIT = 4 };  // TRI_UNIT: flag bit of the kernels' argument
+
 // One operand as the kernels see it: vector v = row of op(A) or column of op(B),
 // element e runs along k.  contig: element e of vector v is at ptr[v*ld + e]
 // (B op N, A op T); otherwise at ptr[e*ld + v] (A op N, B op T).
@@ -69,6 +71,11 @@ struct OperandDesc {
     bool dbl;      // real part is f64 (else f32)
     bool cplx;
     bool conj;     // op C of a complex operand
+    // triangular operand (gemmul8_trmm; real, single-operand launches only): element e of vector v is taken from
+    // memory only inside the kept range -- TRI_LE: e <= v, TRI_GE: e >= v -- and is exactly 0 outside it, whatever
+    // the memory holds; unit: e == v is exactly 1 and not read either
+    int tri = TRI_NONE;
+    bool unit = false;
 };
 
 // ---- split.hip ----
@@ -167,10 +174,21 @@ bool gemm_i8_syrk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
 // domain as gemm_i8_syrk, the units counted as 3 N P; false (nothing launched) outside the domain
 bool gemm_i8_herk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, bool upper, uint8_t *R,
                   const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed);
+// Residue products with one operand's slices those of a triangular matrix (gemmul8_trmm; gemm_i8_trmm_kernel /
+// gemm_i8_trmm_onetile_kernel): every tile of the N residue planes R, each over the k-steps its triangle leaves
+// nonzero.  With t the tile's index along the clipped dimension (on_n: tn, else tm) and K = L.ksteps:
+// hi = false ("k <= t") steps [0, min(K, 4 (t + 1))), hi = true ("k >= t") steps [4 t, K); queue as gemm_i8.
+// false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB, forced flat DMA, sub-products)
+struct KClip {
+    bool on_n, hi;
+};
+bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, KClip clip, uint8_t *R,
+                  const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed);
 // the residue-product kernel of the last RESIDUE launch: 0 none yet, 1 one-tile (gemm_i8_kernel),
 // 2 persistent (gemm_i8_persistent_kernel), 3 k-chunked one-tile launches, 4 128 x 128 (gemm_i8_small_kernel),
 // 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit, 8 / 9 SYRK
-// persistent / one-unit, 10 / 11 HERK persistent / one-unit; g_last_tail_small: its last planes ran as 128 x 128 tiles
+// persistent / one-unit, 10 / 11 HERK persistent / one-unit, 12 / 13 TRMM persistent / one-unit;
+// g_last_tail_small: its last planes ran as 128 x 128 tiles
 extern std::atomic<int> g_last_residue_kernel;
 extern std::atomic<int> g_last_tail_small;
 // exhaustive exactness check of the residue epilogues (0 = biased, 1 = signed): mismatch count

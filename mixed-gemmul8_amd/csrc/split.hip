@@ -175,6 +175,25 @@ __device__ __forceinline__ void load_elem(const R *__restrict__ X, size_t idx, R
     }
 }
 
+// Triangular operand (OperandDesc::tri, gemmul8_trmm; real): element e of vector v is read only inside the kept
+// range (TRI_GE: e >= v, else e <= v); outside it is exactly 0 and with TRI_UNIT e == v is exactly 1, neither taken
+// from memory (which may hold anything, NaN included).  A zero leaves amax and the round-up sum of squares as they
+// are (s + 0 * 0 = s exactly), so the bodies below keep their loops and their order of operations.  TRI = false
+// folds to load_elem: the instantiations of the dense entry points keep their code.
+template <typename R, bool CPLX, bool NT, bool TRI>
+__device__ __forceinline__ void load_op(const R *__restrict__ X, size_t idx, size_t e, size_t v, int tri, R &re, R &im) {
+    if constexpr (TRI) {
+        static_assert(!CPLX, "triangular operands are real");
+        const bool diag = (tri & TRI_UNIT) && e == v;
+        const bool keep = (tri & TRI_GE) ? e >= v : e <= v;
+        re = diag ? R(1) : R(0);
+        im = 0;
+        if (keep && !diag) re = NT ? __builtin_nontemporal_load(X + idx) : X[idx];
+    } else {
+        load_elem<R, CPLX, NT>(X, idx, re, im);
+    }
+}
+
 // s + x*x rounded upward (the reference's __fma_ru on the sum of squares, scaling.hpp:155-213) as
 // inline code: the OCML helper behind __fma_ru is a call whose entry waits for every memory access
 // in flight (s_waitcnt 0), which held each load of the stats passes behind the previous element's
@@ -241,10 +260,10 @@ __device__ __forceinline__ void accum(R re, R im, R &amax, R &sum) {
 // ------------------------------------------------------------------
 // vector v by the VT threads t = 0..VT-1 of a block (or of one half of a 2 VT block: every thread of
 // the block must call it, it holds a barrier); v >= nvec computes nothing and stores nothing
-template <typename R, bool CPLX, int VT, bool ACCU, bool NT = false>
+template <typename R, bool CPLX, int VT, bool ACCU, bool NT = false, bool TRI = false>
 __device__ __forceinline__ void stats_contig_body(const R *__restrict__ X, size_t ld, size_t len, size_t nvec,
                                                   float log2M, int16_t *__restrict__ sft_out, size_t v, int t,
-                                                  R (&grp)[32], R (&gmax)[8]) {
+                                                  R (&grp)[32], R (&gmax)[8], int tri = 0) {
     const int lane = t & 63, w = t >> 6;
     const R *__restrict__ x = X + (CPLX ? 2 : 1) * (v < nvec ? v : 0) * ld;
     if (v >= nvec) len = 0;
@@ -256,13 +275,13 @@ __device__ __forceinline__ void stats_contig_body(const R *__restrict__ X, size_
     for (; e + (U - 1) * VT < len; e += U * VT) {
         R re[U], im[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_elem<R, CPLX, NT>(x, e + u * VT, re[u], im[u]);
+        for (int u = 0; u < U; ++u) load_op<R, CPLX, NT, TRI>(x, e + u * VT, e + u * VT, v, tri, re[u], im[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) accum<R, CPLX, !ACCU>(re[u], im[u], amax, sum);
     }
     for (; e < len; e += VT) {
         R re, im;
-        load_elem<R, CPLX, NT>(x, e, re, im);
+        load_op<R, CPLX, NT, TRI>(x, e, e, v, tri, re, im);
         accum<R, CPLX, !ACCU>(re, im, amax, sum);
     }
     amax = wave_max<R>(amax);
@@ -293,6 +312,16 @@ __global__ __launch_bounds__(VT) void stats_contig_kernel(const R *__restrict__ 
     __shared__ R gmax[8];
     stats_contig_body<R, CPLX, VT, ACCU, NT>(X, ld, len, nvec, log2M, sft_out, blockIdx.x, threadIdx.x, grp, gmax);
 }
+// the same pass over a triangular operand (tri: TRI_LE / TRI_GE, | TRI_UNIT)
+template <typename R, int VT, bool ACCU>
+__global__ __launch_bounds__(VT) void stats_contig_tri_kernel(const R *__restrict__ X, size_t ld, size_t len,
+                                                             size_t nvec, float log2M, int16_t *__restrict__ sft_out,
+                                                             int tri) {
+    __shared__ R grp[32];
+    __shared__ R gmax[8];
+    stats_contig_body<R, false, VT, ACCU, false, true>(X, ld, len, nvec, log2M, sft_out, blockIdx.x, threadIdx.x, grp,
+                                                       gmax, tri);
+}
 
 // ------------------------------------------------------------------
 // pass 1b: strided vectors (A op N, B op T): ROWS vectors per 256-thread block, swept
@@ -308,10 +337,10 @@ template <typename R, int VT, int ROWS> struct StridedShared {
     R part[ROWS][VT + 1];
     R pmax[ROWS][256 / ROWS + 1];
 };
-template <typename R, bool CPLX, int VT, bool ACCU, int ROWS, bool NT = false>
+template <typename R, bool CPLX, int VT, bool ACCU, int ROWS, bool NT = false, bool TRI = false>
 __device__ __forceinline__ void stats_strided_body(const R *__restrict__ X, size_t ld, size_t len, size_t nvec,
                                                    float log2M, int16_t *__restrict__ sft_out, unsigned bx,
-                                                   StridedShared<R, VT, ROWS> &sh) {
+                                                   StridedShared<R, VT, ROWS> &sh, int tri = 0) {
     constexpr int SLOTS = 256 / ROWS;
     constexpr int NA = VT / SLOTS;
     // loads in flight per thread: U * NA (OZ2_STRIDED_LOADS; probe builds vary it)
@@ -333,7 +362,10 @@ __device__ __forceinline__ void stats_strided_body(const R *__restrict__ X, size
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int c = 0; c < NA; ++c) load_elem<R, CPLX, NT>(X, (b + u * VT + slot + SLOTS * c) * ld + v, re[u][c], im[u][c]);
+                for (int c = 0; c < NA; ++c) {
+                    const size_t e = b + u * VT + slot + SLOTS * c;
+                    load_op<R, CPLX, NT, TRI>(X, e * ld + v, e, v, tri, re[u][c], im[u][c]);
+                }
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -342,7 +374,10 @@ __device__ __forceinline__ void stats_strided_body(const R *__restrict__ X, size
         for (; b + VT <= len; b += VT) {
             R re[NA], im[NA];
 #pragma unroll
-            for (int c = 0; c < NA; ++c) load_elem<R, CPLX, NT>(X, (b + slot + SLOTS * c) * ld + v, re[c], im[c]);
+            for (int c = 0; c < NA; ++c) {
+                const size_t e = b + slot + SLOTS * c;
+                load_op<R, CPLX, NT, TRI>(X, e * ld + v, e, v, tri, re[c], im[c]);
+            }
 #pragma unroll
             for (int c = 0; c < NA; ++c) accum<R, CPLX, !ACCU>(re[c], im[c], amax, acc[c]);
         }
@@ -352,7 +387,7 @@ __device__ __forceinline__ void stats_strided_body(const R *__restrict__ X, size
                 const size_t e = b + slot + SLOTS * c;
                 if (e < len) {
                     R re, im;
-                    load_elem<R, CPLX, NT>(X, e * ld + v, re, im);
+                    load_op<R, CPLX, NT, TRI>(X, e * ld + v, e, v, tri, re, im);
                     accum<R, CPLX, !ACCU>(re, im, amax, acc[c]);
                 }
             }
@@ -400,6 +435,15 @@ __global__ __launch_bounds__(256) void stats_strided_kernel(const R *__restrict_
     __shared__ StridedShared<R, VT, ROWS> sh;
     const unsigned bx = ROWS < 16 && OZ2_STATS_XCD ? xcd_local_block(blockIdx.x, gridDim.x) : blockIdx.x;
     stats_strided_body<R, CPLX, VT, ACCU, ROWS, NT>(X, ld, len, nvec, log2M, sft_out, bx, sh);
+}
+// the same pass over a triangular operand (tri: TRI_LE / TRI_GE, | TRI_UNIT)
+template <typename R, int VT, bool ACCU, int ROWS>
+__global__ __launch_bounds__(256) void stats_strided_tri_kernel(const R *__restrict__ X, size_t ld, size_t len,
+                                                               size_t nvec, float log2M,
+                                                               int16_t *__restrict__ sft_out, int tri) {
+    __shared__ StridedShared<R, VT, ROWS> sh;
+    const unsigned bx = ROWS < 16 && OZ2_STATS_XCD ? xcd_local_block(blockIdx.x, gridDim.x) : blockIdx.x;
+    stats_strided_body<R, false, VT, ACCU, ROWS, false, true>(X, ld, len, nvec, log2M, sft_out, bx, sh, tri);
 }
 
 // Both operands' fast-mode shifts in one launch (small problems, one stream; real f64, A rows strided,
@@ -733,12 +777,12 @@ __device__ __forceinline__ int16_t accurate_sft(int16_t sft0, int32_t amax, floa
     const int s = sft0_stored(sft0) + __float2int_rd(__fmaf_rd(-0.51F, __log2f(__int2float_rn(amax)), log2M));
     return (int16_t)(-s);
 }
-template <typename R, bool CPLX, bool CONTIG, bool IS_A, int MODE, bool NTL = false, bool ACC = false>
+template <typename R, bool CPLX, bool CONTIG, bool IS_A, int MODE, bool NTL = false, bool ACC = false, bool TRI = false>
 __device__ __forceinline__ void encode_body(const R *__restrict__ X, size_t ld, size_t nvec, size_t len,
                                             const int16_t *__restrict__ sft, int8_t *__restrict__ out, size_t plane,
                                             size_t ksteps, size_t kblk, size_t vmax, int flags, const ModParams &MP,
                                             const ModGroups &G, unsigned bx, unsigned by, EncTile<R, CPLX> &tile,
-                                            const AccShift *acc = nullptr) {
+                                            const AccShift *acc = nullptr, int tri = 0) {
     constexpr int KT = CPLX ? 32 : 64;
     constexpr int NT = CPLX ? 128 : 256;
     constexpr int NC = CPLX ? 2 : 1;
@@ -765,11 +809,20 @@ __device__ __forceinline__ void encode_body(const R *__restrict__ X, size_t ld, 
     // load without per-element guards so all loads are in flight at once
     constexpr int NL = (64 * KT) / NT;
     const bool interior = v0 + 64 <= nvec && e0 + KT <= len;
+    // triangular operand: a tile wholly outside the kept range issues no loads (its zero slices are still written:
+    // the planes stay fully defined); inside a straddling tile load_op reads the kept elements only
+    const bool dead = TRI && ((tri & TRI_GE) ? e0 + KT <= v0 : e0 > v0 + 63);
     R lre[NL], lim[NL];
     if (OZ2_ENC_ABLATE == 2) {  // probe builds only: no loads
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             lre[i] = (R)(tid * 37 + i * 1.25 + v0);
+            lim[i] = 0;
+        }
+    } else if (dead) {  // block-uniform
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            lre[i] = 0;
             lim[i] = 0;
         }
     } else if (interior) {  // block-uniform branch: one batch of unguarded loads
@@ -779,7 +832,7 @@ __device__ __forceinline__ void encode_body(const R *__restrict__ X, size_t ld, 
             int vl, el;
             if (CONTIG) { el = idx % KT; vl = idx / KT; } else { vl = idx & 63; el = idx >> 6; }
             const size_t v = v0 + vl, e = e0 + el;
-            load_elem<R, CPLX, NTL>(X, CONTIG ? v * ld + e : e * ld + v, lre[i], lim[i]);
+            load_op<R, CPLX, NTL, TRI>(X, CONTIG ? v * ld + e : e * ld + v, e, v, tri, lre[i], lim[i]);
         }
     } else {
 #pragma unroll
@@ -790,7 +843,7 @@ __device__ __forceinline__ void encode_body(const R *__restrict__ X, size_t ld, 
             const size_t v = v0 + vl, e = e0 + el;
             lre[i] = 0;
             lim[i] = 0;
-            if (v < nvec && e < len) load_elem<R, CPLX, NTL>(X, CONTIG ? v * ld + e : e * ld + v, lre[i], lim[i]);
+            if (v < nvec && e < len) load_op<R, CPLX, NTL, TRI>(X, CONTIG ? v * ld + e : e * ld + v, e, v, tri, lre[i], lim[i]);
         }
     }
 #pragma unroll
@@ -836,6 +889,18 @@ __global__ __launch_bounds__(CPLX ? 128 : 256) void encode_kernel(const R *__res
     if (MP.zero_queue && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8) MP.zero_queue[threadIdx.x] = 0;
     encode_body<R, CPLX, CONTIG, IS_A, MODE, NTL>(X, ld, nvec, len, sft, out, plane, ksteps, kblk, vmax, flags, MP, G,
                                              blockIdx.x, blockIdx.y, tile);
+}
+// the same encode of a triangular operand (real; tri: TRI_LE / TRI_GE, | TRI_UNIT)
+template <typename R, bool CONTIG, int MODE>
+__global__ __launch_bounds__(256) void encode_tri_kernel(const R *__restrict__ X, size_t ld, size_t nvec, size_t len,
+                                                        const int16_t *__restrict__ sft, int8_t *__restrict__ out,
+                                                        size_t plane, size_t ksteps, size_t kblk, size_t vmax,
+                                                        int flags, ModParams MP, ModGroups G, int tri) {
+    __shared__ EncTile<R, false> tile;
+    if (MP.zero_queue && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8) MP.zero_queue[threadIdx.x] = 0;
+    encode_body<R, false, CONTIG, false, MODE, false, false, true>(X, ld, nvec, len, sft, out, plane, ksteps, kblk, vmax,
+                                                                   flags, MP, G, blockIdx.x, blockIdx.y, tile, nullptr,
+                                                                   tri);
 }
 
 // ------------------------------------------------------------------
@@ -1419,8 +1484,28 @@ constexpr size_t NT_OPERAND_BYTES = size_t(1) << 27;
 
 template <typename R, bool CPLX>
 static void launch_stats(const void *X, size_t ld, bool contig, size_t len, size_t nvec, int VT, bool accurate,
-                         float log2M, int16_t *out, hipStream_t st) {
+                         float log2M, int16_t *out, hipStream_t st, int tri = 0) {
     const R *x = static_cast<const R *>(X);
+    if constexpr (!CPLX) {
+        if (tri) {  // triangular operand: the same grids, the kernels that honour the kept range (plain loads)
+            if (contig) {
+#define OZ2_SCT(vt, ac) launch(stats_contig_tri_kernel<R, vt, ac>, dim3((unsigned)nvec), dim3(vt), st, x, ld, len, nvec, log2M, out, tri)
+                if (VT == 512) { if (accurate) OZ2_SCT(512, true); else OZ2_SCT(512, false); }
+                else { if (accurate) OZ2_SCT(128, true); else OZ2_SCT(128, false); }
+#undef OZ2_SCT
+            } else {
+                const int rows = stats_rows(nvec);
+                const unsigned g = (unsigned)((nvec + rows - 1) / rows);
+#define OZ2_SST(vt, ac) do { if (rows == 16) launch(stats_strided_tri_kernel<R, vt, ac, 16>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); \
+                             else if (rows == 8) launch(stats_strided_tri_kernel<R, vt, ac, 8>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); \
+                             else launch(stats_strided_tri_kernel<R, vt, ac, 4>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); } while (0)
+                if (VT == 512) { if (accurate) OZ2_SST(512, true); else OZ2_SST(512, false); }
+                else { if (accurate) OZ2_SST(128, true); else OZ2_SST(128, false); }
+#undef OZ2_SST
+            }
+            return;
+        }
+    }
     const bool nt = nvec * len * sizeof(R) * (CPLX ? 2 : 1) >= NT_OPERAND_BYTES;
     if (contig) {
 #define OZ2_SC(vt, ac) do { if (nt) launch(stats_contig_kernel<R, CPLX, vt, ac, true>, dim3((unsigned)nvec), dim3(vt), st, x, ld, len, nvec, log2M, out); \
@@ -1445,7 +1530,7 @@ static void launch_stats(const void *X, size_t ld, bool contig, size_t len, size
 template <typename R, bool CPLX, bool IS_A>
 static void launch_encode(const void *X, size_t ld, bool contig, size_t nvec, size_t len, const int16_t *sft,
                           int8_t *out, size_t plane, const Layout &L, size_t vpad_grid, size_t vmax, int mode,
-                          int flags, const ModParams &MP, hipStream_t st) {
+                          int flags, const ModParams &MP, hipStream_t st, int tri = 0) {
     constexpr int KT = CPLX ? 32 : 64;
     constexpr int NT = CPLX ? 128 : 256;
     if (L.kblk == 0 || vpad_grid == 0) return;  // k = 0: the slice planes are empty
@@ -1467,20 +1552,37 @@ static void launch_encode(const void *X, size_t ld, bool contig, size_t nvec, si
     if constexpr (std::is_same<R, float>::value) {
         if (mode == 0 && !G.f32_exact) mode = 2;
     }
+    if constexpr (!CPLX && !IS_A) {
+        if (tri) {  // triangular operand: the same grid, the kernels that honour the kept range (plain loads)
+#define OZ2_ENT(cg, md) launch(encode_tri_kernel<R, cg, md>, grid, dim3(NT), st, x, ld, nvec, len, sft, out, plane, L.ksteps, L.kblk, vmax, flags, MP, G, tri)
+#define OZ2_ENT_F32(cg) do { if constexpr (std::is_same<R, float>::value) OZ2_ENT(cg, 2); } while (0)
+            if (contig) { if (mode == 0) OZ2_ENT(true, 0); else if (mode == 1) OZ2_ENT(true, 1); else OZ2_ENT_F32(true); }
+            else { if (mode == 0) OZ2_ENT(false, 0); else if (mode == 1) OZ2_ENT(false, 1); else OZ2_ENT_F32(false); }
+#undef OZ2_ENT_F32
+#undef OZ2_ENT
+            return;
+        }
+    }
     if (contig) { if (mode == 0) OZ2_EN(true, 0); else if (mode == 1) OZ2_EN(true, 1); else OZ2_EN_F32(true); }
     else { if (mode == 0) OZ2_EN(false, 0); else if (mode == 1) OZ2_EN(false, 1); else OZ2_EN_F32(false); }
 #undef OZ2_EN_F32
 #undef OZ2_EN
 }
 
+// the kernels' triangle argument of a (real) operand: 0, or TRI_LE / TRI_GE with the TRI_UNIT bit
+static int tri_arg(const OperandDesc &d) {
+    return d.cplx || d.tri == TRI_NONE ? 0 : d.tri | (d.unit ? TRI_UNIT : 0);
+}
+
 void split_stats(const OperandDesc &d, size_t len, size_t nvec, int VT, bool accurate, float log2M, int16_t *out,
                  hipStream_t st) {
+    const int tri = tri_arg(d);
     if (d.dbl) {
         if (d.cplx) launch_stats<double, true>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st);
-        else launch_stats<double, false>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st);
+        else launch_stats<double, false>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st, tri);
     } else {
         if (d.cplx) launch_stats<float, true>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st);
-        else launch_stats<float, false>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st);
+        else launch_stats<float, false>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st, tri);
     }
 }
 
@@ -1495,7 +1597,7 @@ void split_encode(const OperandDesc &d, bool is_A, size_t nvec, size_t len, cons
     size_t vpad = kara ? (is_A ? L.vsA : L.vsB) : is_A ? (d.cplx ? L.m_pad - L.m : L.m_pad) : L.n_pad;
     vpad = round_up(vpad, 64);
     const size_t vmax = kara ? (is_A ? L.vsA : L.vsB) : is_A ? L.m_pad : L.n_pad;
-#define OZ2_LE(R, C, A) launch_encode<R, C, A>(d.ptr, d.ld, d.contig, nvec, len, sft, out, plane, L, vpad, vmax, mode, flags, MP, st)
+#define OZ2_LE(R, C, A) launch_encode<R, C, A>(d.ptr, d.ld, d.contig, nvec, len, sft, out, plane, L, vpad, vmax, mode, flags, MP, st, tri_arg(d))
     if (d.dbl) {
         if (d.cplx) { if (is_A) OZ2_LE(double, true, true); else OZ2_LE(double, true, false); }
         else OZ2_LE(double, false, false);
@@ -1508,7 +1610,7 @@ void split_encode(const OperandDesc &d, bool is_A, size_t nvec, size_t len, cons
 
 bool split_magnitudes(const OperandDesc &d, bool is_A, size_t nvec, size_t len, int16_t *sft0, int8_t *out,
                       const Layout &L, void *scratch, size_t scratch_bytes, hipStream_t st) {
-    if (d.cplx || L.kblk == 0) return false;
+    if (d.cplx || d.tri || L.kblk == 0) return false;  // (a triangular operand: split_stats + split_encode)
     const size_t vpad = round_up(is_A ? L.m_pad : L.n_pad, 64), ktiles = L.kblk / 64;
     if (scratch_bytes < ktiles * vpad * sizeof(int2) + vpad * sizeof(int)) return false;
     if (d.contig && vpad / 64 > 65536) return false;
@@ -1539,7 +1641,7 @@ bool split_magnitudes_pair(const OperandDesc &dA, size_t m, const OperandDesc &d
                            int16_t *sft0A, int16_t *sft0B, int8_t *outA, int8_t *outB, const Layout &L,
                            void *scratchA, size_t bytesA, void *scratchB, size_t bytesB, int32_t *bound,
                            size_t nbound, hipStream_t st) {
-    if (dA.cplx || dB.cplx || dA.dbl != dB.dbl || L.kblk == 0 || m == 0 || n == 0) return false;
+    if (dA.cplx || dB.cplx || dA.tri || dB.tri || dA.dbl != dB.dbl || L.kblk == 0 || m == 0 || n == 0) return false;
     const size_t ktiles = L.kblk / 64;
     auto operand = [&](const OperandDesc &d, size_t nvec, size_t vpad_rows, int16_t *sft0, int8_t *out,
                        void *scratch, size_t bytes, MagOperand &o) {
@@ -1591,8 +1693,8 @@ template <bool MAG>
 static bool fused_pair_launch(const OperandDesc &dA, size_t m, const OperandDesc &dB, size_t n, size_t len,
                               float log2M, int16_t *sftA, int16_t *sftB, int8_t *outA, int8_t *outB, const Layout &L,
                               const ModParams &MP, int32_t *zero, size_t nzero, hipStream_t st) {
-    if (!fused_split_mode() || dA.cplx || dB.cplx || !dA.dbl || !dB.dbl || L.kara || L.kblk == 0 || L.kblk > 2048 ||
-        m == 0 || n == 0)
+    if (!fused_split_mode() || dA.cplx || dB.cplx || dA.tri || dB.tri || !dA.dbl || !dB.dbl || L.kara || L.kblk == 0 ||
+        L.kblk > 2048 || m == 0 || n == 0)
         return false;
     FusedOperand a{}, b{};
     a.X = static_cast<const double *>(dA.ptr);
@@ -1693,7 +1795,8 @@ void split_finalize_accurate_pair(const int16_t *sft0A, const int32_t *boundA, s
 
 bool split_stats_pair(const OperandDesc &dA, size_t m, const OperandDesc &dB, size_t n, size_t len, int VT,
                       float log2M, int16_t *sftA, int16_t *sftB, hipStream_t st) {
-    if (dA.cplx || dB.cplx || !dA.dbl || !dB.dbl || dA.contig || !dB.contig || VT != 128) return false;
+    if (dA.cplx || dB.cplx || dA.tri || dB.tri || !dA.dbl || !dB.dbl || dA.contig || !dB.contig || VT != 128)
+        return false;
     const int rows = stats_rows(m);
     const unsigned ga = (unsigned)((m + rows - 1) / rows), gb = (unsigned)((n + 1) / 2);
     const double *a = static_cast<const double *>(dA.ptr), *b = static_cast<const double *>(dB.ptr);
@@ -1734,7 +1837,7 @@ bool split_encode_pair(const OperandDesc &dA, size_t m, const OperandDesc &dB, s
                        const int16_t *sftA, const int16_t *sftB, int8_t *outA, int8_t *outB, const Layout &L,
                        const ModParams &MP, hipStream_t st, const AccurateShifts *accs) {
     // operands of one element type (the same ModGroups and tile type); anything else: two launches
-    if (dA.cplx != dB.cplx || dA.dbl != dB.dbl || L.kblk == 0) return false;
+    if (dA.cplx != dB.cplx || dA.dbl != dB.dbl || dA.tri || dB.tri || L.kblk == 0) return false;
     if (accs && (dA.cplx || L.kara)) return false;  // (real operands only: complex A rows take two bound maxima)
     const bool cplx = dA.cplx;
     const int KT = cplx ? 32 : 64;

@@ -21,6 +21,8 @@ LIB_PATH = os.path.join(_HERE, "libgemmul8_amd.so")
 REAL_DEFAULT, COMPLEX_BIG_MATRIX_ENCODE, COMPLEX_CLASSIC_MULT, COMPLEX_KARATSUBA_MULT = 0, 1, 2, 3
 OP_N, OP_T, OP_C = 0, 1, 2
 FILL_LOWER, FILL_UPPER = 0, 1
+SIDE_LEFT, SIDE_RIGHT = 0, 1
+DIAG_NON_UNIT, DIAG_UNIT = 0, 1
 R_64F, R_32F, C_64F, C_32F = 0, 1, 2, 3
 _DTYPE = {torch.float64: R_64F, torch.float32: R_32F, torch.complex128: C_64F, torch.complex64: C_32F}
 _ERR = {-1: "num_moduli outside [2, 20]", -2: "unsupported dtype combination for computeType",
@@ -68,6 +70,10 @@ def _load():
     lib.gemmul8_work_size_herk.argtypes = [sz, sz, u]
     lib.gemmul8_herk.restype = i
     lib.gemmul8_herk.argtypes = [p, i, i, sz, sz, i, i, p, p, sz, p, p, sz, u, i, p, d]
+    lib.gemmul8_work_size_trmm.restype = sz
+    lib.gemmul8_work_size_trmm.argtypes = [i, sz, sz, u]
+    lib.gemmul8_trmm.restype = i
+    lib.gemmul8_trmm.argtypes = [p, i, i, i, i, sz, sz, i, i, i, p, p, sz, p, sz, p, sz, u, i, p, d]
     lib.gemmul8_timing_enable.argtypes = [i]
     lib.gemmul8_timing_read.argtypes = [d, ctypes.POINTER(ctypes.c_int)]
     lib.gemmul8_layout.argtypes = [sz, sz, sz, u, i, ctypes.POINTER(ctypes.c_size_t)]
@@ -218,6 +224,27 @@ def herk(uplo, trans, n, k, alpha, A, lda, beta, C, ldc, num_moduli, fastmode, w
     pt = (ctypes.c_double * 4)() if phase_times else None
     _check(lib.gemmul8_herk(_stream(stream), uplo, trans, n, k, ta, tc, al.ptr, A.data_ptr(), lda, be.ptr,
                             C.data_ptr(), ldc, num_moduli, int(bool(fastmode)), work.data_ptr(), pt))
+    return list(pt) if phase_times else None
+
+
+def workSize_trmm(side, m, n, num_moduli):
+    """Bytes of device workspace for trmm: workSize(m, n, m if side == SIDE_LEFT else n, num_moduli)."""
+    return int(lib.gemmul8_work_size_trmm(side, m, n, num_moduli))
+
+
+def trmm(side, uplo, trans, diag, m, n, alpha, A, lda, B, ldb, C, ldc, num_moduli, fastmode, work, stream=None,
+         phase_times=False):
+    """C = alpha*op(A)*B (SIDE_LEFT, A m x m) or alpha*B*op(A) (SIDE_RIGHT, A n x n) on column-major real device
+    buffers, A triangular: only its `uplo` triangle is read (DIAG_UNIT: not the diagonal either, which counts as 1),
+    the rest may hold anything.  B and C are m x n; C is not read and may be B itself (ldc == ldb, one dtype).  C has
+    the bits gemm writes with beta = 0 for A's explicit dense form.  work holds workSize_trmm bytes.  Returns the
+    phase times like gemm."""
+    ta, tb, tc = _DTYPE[A.dtype], _DTYPE[B.dtype], _DTYPE[C.dtype]
+    al = _scalar(alpha, C.dtype)
+    pt = (ctypes.c_double * 4)() if phase_times else None
+    _check(lib.gemmul8_trmm(_stream(stream), side, uplo, trans, diag, m, n, ta, tb, tc, al.ptr, A.data_ptr(), lda,
+                            B.data_ptr(), ldb, C.data_ptr(), ldc, num_moduli, int(bool(fastmode)), work.data_ptr(),
+                            pt))
     return list(pt) if phase_times else None
 
 

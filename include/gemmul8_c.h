@@ -39,7 +39,10 @@ enum {
     GEMMUL8_E_HIP = -6           /* a HIP launch or runtime call failed */
 };
 
-/* bytes of workspace required by gemmul8_gemm for this shape (0 for an unknown compute_type) */
+/* bytes of workspace required by gemmul8_gemm for this shape (0 for an unknown compute_type).  A function of the
+ * shape alone, not of the device.  Shapes of at most 64 output tiles of 256 x 256 and at least 256 k-steps of 64
+ * (no Karatsuba sub-products) carry 16 MiB more behind every other area: the partial tiles and arrival counters of
+ * the split-K products ("gemm_i8_splitk_kernel"). */
 size_t gemmul8_work_size(size_t m, size_t n, size_t k, unsigned num_moduli, int compute_type);
 
 /* C = alpha * op(A) * op(B) + beta * C, emulated with num_moduli int8 products.
@@ -168,7 +171,11 @@ int gemmul8_trmm(void *stream, int side, int uplo, int trans, int diag, size_t m
  *
  * One workspace may serve several gemmul8_products / _products_cols launches in flight on
  * different streams only when their mod_begin differ (each first modulus has its own tile-queue
- * heads); launches ordered on one stream may share anything. */
+ * heads); launches ordered on one stream may share anything.
+ *
+ * The phase entry points never split k: gemmul8_products / _products_cols run one block per output tile and
+ * modulus over the whole of k (in sequential chunks beyond padded k = 2^17) at every shape.  gemmul8_gemm runs
+ * launches of few tiles and long k as "gemm_i8_splitk_kernel", whose residues are the same bytes. */
 enum { GEMMUL8_SPLIT_BOUND_READY = 1, GEMMUL8_SPLIT_SHIFTS_READY = 2 };
 int gemmul8_split_bound(void *stream, int op_a, int op_b, size_t m, size_t n, size_t k, int type_a, int type_b,
                         int type_c, const void *A, size_t lda, const void *B, size_t ldb, unsigned num_moduli,
@@ -286,7 +293,8 @@ int gemmul8_get_epilogue(void);
  * ("gemm_i8_persistent_pg_kernel", "gemm_i8_persistent_kernel", "gemm_i8_kernel", "gemm_i8_small_kernel",
  * "gemm_i8_kernel (k-chunked)", "gemm_i8_batched_kernel", "gemm_i8_batched_onetile_kernel", "gemm_i8_syrk_kernel",
  * "gemm_i8_syrk_onetile_kernel", "gemm_i8_herk_kernel", "gemm_i8_herk_onetile_kernel", "gemm_i8_trmm_kernel",
- * "gemm_i8_trmm_onetile_kernel" or "none"; a gemmul8_syrk, gemmul8_herk or gemmul8_trmm call outside its own
+ * "gemm_i8_trmm_onetile_kernel", "gemm_i8_splitk_kernel" (gemmul8_gemm and its low-memory, strided-batched-fallback
+ * and timing forms only: few output tiles, long k) or "none"; a gemmul8_syrk, gemmul8_herk or gemmul8_trmm call outside its own
  * kernels' domain reports the gemm kernel that ran all tiles). */
 const char *gemmul8_last_products_kernel(void);
 

@@ -323,6 +323,8 @@ __device__ __forceinline__ int acc_col(int jj, int lane) { return jj * 32 + (lan
 constexpr int ACC_E = 16;
 #endif
 
+constexpr int PARK_CS = 68;  // column stride (dwords) of the residues parked in LDS, see epilogue
+
 // Epilogues over the 8 compute waves' accumulators (active = this wave holds a 128 x 64 block;
 // every thread of the block must call it: it contains block barriers).  plane: the residue plane written (the
 // modulus j, or the batched kernels' pair index).
@@ -336,7 +338,6 @@ __device__ __forceinline__ void epilogue(const GemmArgs &g, AccTile (&acc)[ACC_I
         // over the banks (two lanes per bank), and every write of a lane is ONE base address plus an immediate
         // offset (the XOR-swizzled layout before it cost ~5 address instructions per write and a runtime dword
         // permutation per 16-byte read; tools/probes/onetile_ablate.hip)
-        constexpr int PARK_CS = 68;
         static_assert(256 * PARK_CS * 4 <= LDS_BYTES, "park area");
         uint32_t *lo = reinterpret_cast<uint32_t *>(smem);
         uint32_t *pbase = lo + (wc * 64 + (lane & 15)) * PARK_CS + wr * 32 + (lane >> 4);
@@ -1612,6 +1613,176 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_batched_onetile_kernel(Ba
 }
 
 // ---------------------------------------------------------------------------------------------
+// Split-K residue products: launches of few output tiles and long k (Gram matrices, CholeskyQR panels:
+// 256^2 .. 1024^2 x 10^5 .. 10^6), where one block per (tile, modulus) unit leaves most CUs idle.  S blocks
+// serve one unit; block s walks the k-steps [s K / S, (s + 1) K / S) with the one-tile kernel's ring, ping-pong
+// main loop and fragment reads.  The residues of disjoint k ranges add mod p in any order (the int8 products
+// are exact), so the planes carry the unsplit product's bytes whichever block finishes last.
+//   Within its range a block runs ONE pipeline; every `chunk` k-steps (<= 2^16 / 64, so |sum| <= 2^30: the biased
+// residue path) each wave folds its own accumulators -- residues of the 128 values, four to a dword, added
+// bytewise mod p to 32 running dwords in registers -- and restarts them from the bias.  No LDS, no barrier and no
+// memory traffic at a chunk boundary: the ring keeps running under it.
+//   At the end the running residues are parked in LDS in the block epilogue's layout and stored as the block's
+// partial, 64 KiB [256 cols][256 rows], to its private slot [unit][s].  Every thread then releases at agent scope,
+// the block meets at a barrier and thread 0 increments the unit's arrival counter (acquire-release, agent scope).
+// The block that reads S - 1 arrived last: every other block's partial is visible to it (their releases precede
+// their increments, its acquire follows its own), so it adds the S slots mod p and writes the unit's tile of the
+// residue plane.  Every other block exits: nobody waits for anybody.  The eight XCDs have separate L2s; the
+// agent-scope fences write the partials back and invalidate the reader's lines, wherever the blocks ran.  The
+// blocks of one unit have consecutive logical ids of the XCD-contiguous remap, so they mostly share an XCD (its
+// L2 then holds the partials), which is locality only.
+struct SplitKArgs {
+    GemmArgs g;         // the launch's geometry: ksteps = kstride = the whole k extent, biased = 1, nsub = 1
+    uint8_t *slots;     // [unit][S] partials of SPLITK_SLOT_BYTES
+    uint32_t *count;    // [unit] arrival counters, zeroed before the launch
+    unsigned S, chunk;  // splits per unit; k-steps per biased chunk
+};
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_splitk_kernel(SplitKArgs a) {
+    static_assert(OZ2_MFMA16, "park map: 16x16 accumulator tiles");
+    __shared__ __attribute__((aligned(1024))) int8_t smem[LDS_BYTES];
+    const GemmArgs &g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 2, wc = wave & 3;
+
+    // logical id: contiguous per XCD (gemm_i8_kernel's remap); unit = id / S, split = id mod S
+    const unsigned nwg = gridDim.x, bid = blockIdx.x;
+    const unsigned xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const unsigned unit = __builtin_amdgcn_readfirstlane(wgid / a.S), sp = wgid - unit * a.S;
+    const TileRef u = decode_tile<false>(g, unit);
+    const unsigned k0 = sp * g.ksteps / a.S, K = (sp + 1) * g.ksteps / a.S - k0;  // S K < 2^32 (host); K >= 1
+
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
+    const uint32_t lds_wave = lds_base + wave * 1024;
+    const v4si rA = make_rsrc(g.A + (size_t)u.j * g.planeA, (uint32_t)g.planeA);
+    const v4si rB = make_rsrc(g.B + (size_t)u.j * g.planeB, (uint32_t)g.planeB);
+    const uint32_t oA = u.offA + k0 * (uint32_t)PANEL + wave * 1024 + lane * 16;
+    const uint32_t oB = u.offB + k0 * (uint32_t)PANEL + wave * 1024 + lane * 16;
+    auto stage = [&](unsigned ks, unsigned slot) {
+        const uint32_t g32 = ks * (uint32_t)PANEL, lo = lds_wave + slot * SLOT;
+        bglds16(rA, oA + g32, lo);
+        bglds16(rA, oA + g32 + 8192, lo + 8192);
+        bglds16(rB, oB + g32, lo + PANEL);
+        bglds16(rB, oB + g32 + 8192, lo + PANEL + 8192);
+    };
+
+    const int p = g.p[u.j], acc0 = g.bias[u.j];
+    const double invp = g.invp[u.j], pneg = -(double)p;
+    const double cneg = __builtin_fma(-0x1p52, invp, 0x1p-8);
+    AccTile acc[ACC_I][ACC_J];
+    uint32_t run[ACC_I][ACC_J];  // residues so far: rows 4 (lane >> 4) + e of tile (i, jj) in byte e
+#pragma unroll
+    for (int i = 0; i < ACC_I; ++i)
+#pragma unroll
+        for (int jj = 0; jj < ACC_J; ++jj) {
+            acc[i][jj] = AccTile{} + acc0;
+            run[i][jj] = 0;
+        }
+    // chunk boundary: run = (run + residues of acc) mod p, acc = bias
+    auto fold_with = [&](auto &&res) {
+#pragma unroll
+        for (int i = 0; i < ACC_I; ++i)
+#pragma unroll
+            for (int jj = 0; jj < ACC_J; ++jj) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w |= res((uint32_t)acc[i][jj][e]) << (8 * e);
+                run[i][jj] = add_mod_bytes(run[i][jj], w, (uint32_t)p);
+                acc[i][jj] = AccTile{} + acc0;
+            }
+    };
+    auto fold = [&] {
+        if (p == 256) fold_with([](uint32_t x) { return x & 0xffu; });  // the bias is a multiple of 256
+        else fold_with([&](uint32_t x) { return residue_biased_f64(x, invp, cneg, pneg); });
+    };
+
+    constexpr unsigned D = STAGES - 1;
+    // barrier accounting as gemm_i8_kernel: 1 + 2K + 1 per group before the epilogue (fold passes none)
+    for (unsigned s0 = 0; s0 < D; ++s0)
+        if (s0 < K) stage(s0, s0);
+    if (K >= D) wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+    else wait_steps_lgkm0<GLDS_PER_STEP>((int)K - 1);
+    barrier();
+    if (wr == 1) barrier();
+    Frags f;
+    unsigned slot_cur = 0, slot_issue = D % STAGES, t = 0, kc = 0;
+    for (; t < K; ++t) {  // one loop for the steady state and the drain: ONE copy of the fold (block-uniform branches)
+        read_frags(f, smem + slot_cur * SLOT, wr, wc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (t + D < K) {
+            stage(t + D, slot_issue);
+            wait_vm_lgkm0<GLDS_PER_STEP *(D - 1)>();
+        } else {  // drain: nothing left to stage, steps t+2..K-1 may fly
+            wait_steps_lgkm0<GLDS_PER_STEP>(t + 2 < K ? (int)(K - t - 2) : 0);
+        }
+        barrier();
+        mfma_step(acc, f);
+        barrier();
+        slot_cur = slot_cur == STAGES - 1 ? 0 : slot_cur + 1;
+        slot_issue = slot_issue == STAGES - 1 ? 0 : slot_issue + 1;
+        if (++kc == a.chunk || t + 1 == K) {  // chunk boundary, or the range's end
+            fold();
+            kc = 0;
+        }
+    }
+    if (wr == 0) barrier();
+    barrier();  // all waves done with the ring before the park reuses it
+
+    // the partial: park as the block epilogue does, then 16-byte chunks in slot order (chunk c = 16 col + qd)
+    uint32_t *lo = reinterpret_cast<uint32_t *>(smem);
+    uint32_t *pbase = lo + (wc * 64 + (lane & 15)) * PARK_CS + wr * 32 + (lane >> 4);
+#pragma unroll
+    for (int i = 0; i < ACC_I; ++i)
+#pragma unroll
+        for (int jj = 0; jj < ACC_J; ++jj) pbase[jj * 16 * PARK_CS + 4 * i] = run[i][jj];
+    __syncthreads();
+    constexpr int CHUNKS = (int)(SPLITK_SLOT_BYTES / 16);  // 4096 per slot, 8 per thread
+    uint4 *slots = reinterpret_cast<uint4 *>(a.slots + (size_t)unit * a.S * SPLITK_SLOT_BYTES);
+    uint4 *mine = slots + (size_t)sp * CHUNKS;
+#pragma unroll
+    for (int it = 0; it < CHUNKS / NTHREADS; ++it) {
+        const int chunk = tid + NTHREADS * it;
+        mine[chunk] = *reinterpret_cast<const uint4 *>(lo + (chunk >> 4) * PARK_CS + 4 * (chunk & 15));
+    }
+
+    // arrival: release (every thread's own stores), barrier, one acquire-release increment per block
+    uint32_t *arrived = lo + 256 * PARK_CS;
+    static_assert(256 * PARK_CS * 4 + 4 <= LDS_BYTES, "arrival word behind the park area");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (tid == 0) *arrived = __hip_atomic_fetch_add(a.count + unit, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (*arrived != a.S - 1) return;  // block-uniform: not the last arriver, nothing to wait for
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+
+    // the last arriver: the S slots added mod p, the unit's tile of the residue plane
+    uint4 sum[CHUNKS / NTHREADS];
+#pragma unroll
+    for (int it = 0; it < CHUNKS / NTHREADS; ++it) sum[it] = slots[tid + NTHREADS * it];
+#pragma unroll 2
+    for (unsigned q = 1; q < a.S; ++q) {
+        uint4 v[CHUNKS / NTHREADS];
+#pragma unroll
+        for (int it = 0; it < CHUNKS / NTHREADS; ++it) v[it] = slots[(size_t)q * CHUNKS + tid + NTHREADS * it];
+#pragma unroll
+        for (int it = 0; it < CHUNKS / NTHREADS; ++it)
+            sum[it] = make_uint4(add_mod_bytes(sum[it].x, v[it].x, (uint32_t)p), add_mod_bytes(sum[it].y, v[it].y, (uint32_t)p),
+                                 add_mod_bytes(sum[it].z, v[it].z, (uint32_t)p), add_mod_bytes(sum[it].w, v[it].w, (uint32_t)p));
+    }
+    uint8_t *out = static_cast<uint8_t *>(g.out) + u.j * g.planeOut + (size_t)u.tn * 256 * g.ldo + (size_t)u.tm * 256;
+#pragma unroll
+    for (int it = 0; it < CHUNKS / NTHREADS; ++it) {
+        const int chunk = tid + NTHREADS * it;
+        typedef unsigned u4v __attribute__((ext_vector_type(4)));
+        u4v *dst = reinterpret_cast<u4v *>(out + (size_t)(chunk >> 4) * g.ldo + 16 * (chunk & 15));
+        const u4v val = u4v{sum[it].x, sum[it].y, sum[it].z, sum[it].w};
+        if (OZ2_RES_NTS) __builtin_nontemporal_store(val, dst);
+        else *dst = val;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Symmetric rank-k residue products (gemmul8_syrk): the tiles of ONE triangle of the n_pad x n_pad residue
 // planes, T (T + 1) / 2 per modulus instead of T^2 (T = n_pad / 256).  The int8 products are exact, so the
 // residue of (i, j) equals that of (j, i): nothing of the other triangle is needed.  Row panel tm comes from
@@ -2383,7 +2554,7 @@ std::atomic<int> g_last_tail_small{0};
 
 void gemm_i8(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned nplanes, Epi epi, void *out,
              int32_t *rowmax, int32_t *colmax, const ModParams &MP, hipStream_t st, uint32_t *queue,
-             bool queue_zeroed, bool tail_small) {
+             bool queue_zeroed, bool tail_small, bool allow_splitk, uint8_t *splitk) {
     GemmArgs g{};
     g.A = A8;
     g.B = B8;
@@ -2429,6 +2600,34 @@ void gemm_i8(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned nplan
         return e ? (unsigned)atoi(e) : 0u;
     }();
     const unsigned chunk = forced_chunk ? forced_chunk : ((1u << 16) / KSTEP);
+    // split-K (gemm_i8_splitk_kernel): few units and long k.  S blocks per unit, as many as fill the CUs once (the
+    // area holds SPLITK_SLOTS partials) with at least SPLITK_MIN_STEPS k-steps each; inside its domain it replaces
+    // the one-tile launch and the sequential chunk launches below.  Only where the caller allows it (gemmul8_gemm's
+    // run(); the phase entry points never split k) and no kernel is forced by the environment.
+    if (epi == Epi::RESIDUE && allow_splitk && splitk && g.nsub == 1 && buf && small_tiles_mode() == 2 &&
+        persistent_mode() == 2) {
+        const unsigned units = (unsigned)(L.mtiles * L.ntiles) * nplanes;
+        const unsigned cus = std::min(device_cu_count(), SPLITK_SLOTS);
+        // GEMMUL8_SPLITK_MIN_STEPS (read per call; tools/probes/splitk_ab.py): another floor on the k-steps per split
+        const char *ms = getenv("GEMMUL8_SPLITK_MIN_STEPS");
+        const unsigned min_steps = ms && atoi(ms) > 0 ? (unsigned)atoi(ms) : SPLITK_MIN_STEPS;
+        const unsigned S = units ? std::min(cus / units, g.ksteps / min_steps) : 0u;
+        if (S >= 2) {
+            SplitKArgs a{};
+            a.g = g;
+            a.g.biased = 1;
+            a.g.nplanes = nplanes;
+            a.slots = splitk;
+            a.count = reinterpret_cast<uint32_t *>(splitk + SPLITK_SLOTS * SPLITK_SLOT_BYTES);
+            a.S = S;
+            a.chunk = std::min(chunk, (1u << 16) / KSTEP);
+            zero_i32(reinterpret_cast<int32_t *>(a.count), units, st);
+            g_last_residue_kernel.store(14, std::memory_order_relaxed);
+            g_last_tail_small.store(0, std::memory_order_relaxed);
+            launch(gemm_i8_splitk_kernel, dim3(units * S), dim3(NTHREADS), st, a);
+            return;
+        }
+    }
     if (epi == Epi::RESIDUE && (L.k_pad > ((size_t)1 << 17) || (forced_chunk && g.ksteps > forced_chunk))) {
         g_last_residue_kernel.store(3, std::memory_order_relaxed);
         g.biased = 1;

@@ -229,6 +229,7 @@ struct Views {
     int16_t *sftA, *sftB, *sft0;
     int32_t *bound;
     uint32_t *queue;
+    uint8_t *splitk;  // split-K area of the products (nullptr: the shape has none)
 };
 // kara: make_layout's (-1 = kara_default for complex; 1 forces the Karatsuba geometry, gemmul8_herk)
 static Views views(void *work, size_t m, size_t n, size_t k, unsigned N, bool cplx, unsigned slice_planes = 0,
@@ -244,6 +245,7 @@ static Views views(void *work, size_t m, size_t n, size_t k, unsigned N, bool cp
     v.bound = reinterpret_cast<int32_t *>(base + v.L.offBound);
     v.sft0 = reinterpret_cast<int16_t *>(base + v.L.offSft0);
     v.queue = reinterpret_cast<uint32_t *>(base + v.L.offQueue);
+    v.splitk = v.L.offSplitK ? reinterpret_cast<uint8_t *>(base + v.L.offSplitK) : nullptr;
     return v;
 }
 
@@ -407,11 +409,13 @@ static void phase_split(const Call &c, const Views &v, unsigned j0, unsigned j1,
 // phase 2: residue planes j0..j1-1 from the slice planes starting at `slot` (one launch;
 // conv_32i_2_8u fused into the epilogue).  queue_zeroed: the A encode just before on this stream
 // zeroed the tile queue (phase_split, operand_encode); otherwise the products zero it themselves.
+// splitk: the launch may split k (run() only: one products launch at a time uses the workspace's split-K area; the
+// phase entry points, whose launches of disjoint moduli may share a workspace on several streams, never do)
 static void phase_products(const Views &v, unsigned N, unsigned j0, unsigned j1, unsigned slot, hipStream_t st,
-                           bool queue_zeroed) {
+                           bool queue_zeroed, bool splitk = false) {
     const Layout &L = v.L;
     gemm_i8(v.A8 + slot * L.planeA, v.B8 + slot * L.planeB, L, j1 - j0, Epi::RESIDUE, v.R + j0 * L.planeR, nullptr,
-            nullptr, sub_mod_params(N, j0, j1), st, queue_of(v, j0), queue_zeroed);
+            nullptr, sub_mod_params(N, j0, j1), st, queue_of(v, j0), queue_zeroed, false, splitk, v.splitk);
 }
 
 // epilogue mode of the process (gemmul8_set_epilogue): 0 BLAS semantics (default), 1 the reference's
@@ -490,7 +494,7 @@ static int run(Call &c, double *phase_ns) {
         split.end();
         if (!launch_ok()) return fail();
         timing::Phase prod(record, c.st, rec.prod0, rec.prod1);
-        phase_products(v, c.N, 0, c.N, 0, c.st, true);
+        phase_products(v, c.N, 0, c.N, 0, c.st, true, true);
         prod.end();
         if (!launch_ok()) return fail();
     } else {
@@ -512,7 +516,7 @@ static int run(Call &c, double *phase_ns) {
             operand_encode(c, v, false, j0, j1, 0, c.stB);
             join(c);
             if (!launch_ok()) return fail();
-            phase_products(v, c.N, j0, j1, 0, c.st, true);
+            phase_products(v, c.N, j0, j1, 0, c.st, true, true);
             if (!launch_ok()) return fail();
         }
         prod.end();
@@ -1294,6 +1298,7 @@ const char *gemmul8_last_products_kernel(void) {
     case 11: return "gemm_i8_herk_onetile_kernel";
     case 12: return "gemm_i8_trmm_kernel";
     case 13: return "gemm_i8_trmm_onetile_kernel";
+    case 14: return "gemm_i8_splitk_kernel";
     default: return "none";
     }
 }

@@ -34,6 +34,13 @@ constexpr int TILE = 256;          // vectors per panel (GEMM block tile edge)
 constexpr int KSTEP = 64;          // k-bytes per panel
 constexpr int PANEL = TILE * KSTEP;  // 16 KiB
 constexpr int QUEUE_HEADS = 8;       // tile-queue heads per products launch (one per XCD)
+// split-K residue products (gemm_i8_splitk_kernel): a launch of few tiles and long k runs S blocks per
+// (tile, modulus) unit, each over 1/S of the k-steps and at least SPLITK_MIN_STEPS of them; S * units <= SPLITK_SLOTS
+// (128: the smallest floor of {32, 64, 128, 256} at which no measured shape lost to the unsplit products,
+// profiles/splitk/ab.jsonl; at 64, 512^2 x 8192 with two splits of 56 units was 5 % slower)
+constexpr unsigned SPLITK_MIN_STEPS = 128;
+constexpr unsigned SPLITK_SLOTS = 256;                      // partial tiles (and arrival counters) of the area
+constexpr size_t SPLITK_SLOT_BYTES = (size_t)TILE * TILE;   // one 256 x 256 uint8 partial
 
 enum class Scal : int { F64 = 0, F32 = 1 };
 
@@ -63,6 +70,7 @@ struct Layout {
     unsigned S;                    // slice planes held at once (= N unless low-memory mode)
     // workspace offsets (bytes)
     size_t offA, offB, offR, offSftA, offSftB, offBound, offSft0, offQueue, total;
+    size_t offSplitK;  // split-K partial slots + arrival counters; 0: the shape has no such area
 };
 
 static inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -143,6 +151,12 @@ static inline Layout make_layout(size_t m, size_t n, size_t k, unsigned N, bool 
     // 8 per-XCD tile-queue heads of the persistent product kernel, one set per first modulus of a
     // products launch: launches of disjoint moduli ranges may share the workspace on different streams
     L.offQueue = off; off += round_up(QUEUE_HEADS * OZ2_MAX_MODULI * 4, 256);
+    // split-K area, for the shapes the split-K rule of gemm_i8 can take (a function of the shape alone: the
+    // workspace size does not depend on the device): SPLITK_SLOTS partial tiles, then as many arrival counters
+    if (L.nsub == 1 && L.mtiles * L.ntiles <= 64 && L.ksteps >= 2 * SPLITK_MIN_STEPS) {
+        L.offSplitK = off;
+        off += round_up(SPLITK_SLOTS * (SPLITK_SLOT_BYTES + 4), 256);
+    }
     L.total = off;
     return L;
 }

@@ -153,9 +153,12 @@ enum class Epi : int { RESIDUE = 0, BOUND = 1, RAW = 2 };
 // (nullptr: one-tile kernel only); queue_zeroed: an earlier launch on st zeroed it (else a zeroing
 // launch precedes the persistent kernel).
 // tail_small: this launch is the 128 x 128 tail of a residue launch (gemm_i8 splits it off itself)
+// allow_splitk, splitk: the residue launch may run as gemm_i8_splitk_kernel (few tiles, long k) with its partials
+// and arrival counters in the workspace's split-K area (base + Layout::offSplitK; nullptr: the shape has none)
 void gemm_i8(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned nplanes, Epi epi, void *out,
              int32_t *rowmax, int32_t *colmax, const ModParams &MP, hipStream_t st, uint32_t *queue = nullptr,
-             bool queue_zeroed = false, bool tail_small = false);
+             bool queue_zeroed = false, bool tail_small = false, bool allow_splitk = false,
+             uint8_t *splitk = nullptr);
 // Residue products of a batch in one launch (gemm_i8_batched_kernel / gemm_i8_batched_onetile_kernel): slice
 // planes [batch][N] ([N] for a shared operand) and residue planes R [batch][N] of the geometry L; queue as gemm_i8.
 // false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB, sub-products)
@@ -187,7 +190,8 @@ bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
 // the residue-product kernel of the last RESIDUE launch: 0 none yet, 1 one-tile (gemm_i8_kernel),
 // 2 persistent (gemm_i8_persistent_kernel), 3 k-chunked one-tile launches, 4 128 x 128 (gemm_i8_small_kernel),
 // 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit, 8 / 9 SYRK
-// persistent / one-unit, 10 / 11 HERK persistent / one-unit, 12 / 13 TRMM persistent / one-unit;
+// persistent / one-unit, 10 / 11 HERK persistent / one-unit, 12 / 13 TRMM persistent / one-unit, 14 split-K
+// (gemm_i8_splitk_kernel);
 // g_last_tail_small: its last planes ran as 128 x 128 tiles
 extern std::atomic<int> g_last_residue_kernel;
 extern std::atomic<int> g_last_tail_small;

@@ -130,7 +130,7 @@ int gemmul8_herk(void *stream, int uplo, int trans, size_t n, size_t k, int type
 
 /* --- triangular matrix multiply --------------------------------------------------------------------
  * side = GEMMUL8_SIDE_LEFT: C = alpha * op(A) * B with A m x m; GEMMUL8_SIDE_RIGHT: C = alpha * B * op(A) with A
- * n x n; op = trans (GEMMUL8_OP_N / OP_T); B and C m x n; column-major.  A is triangular: only its `uplo` triangle is
+ * n x n; op = trans (GEMMUL8_OP_N / OP_T; complex types: also OP_C); B and C m x n; column-major.  A is triangular: only its `uplo` triangle is
  * read, and with GEMMUL8_DIAG_UNIT not its diagonal either, which counts as exactly 1.0; the unreferenced elements
  * never influence the result and may hold anything, NaN and Inf included.  There is no beta (the out-of-place form
  * of rocBLAS / hipBLAS-v2 trmm): C is never read, the CRT runs with beta = 0 under BLAS epilogue semantics
@@ -144,15 +144,28 @@ int gemmul8_herk(void *stream, int uplo, int trans, size_t n, size_t k, int type
  * The split reads the triangle's half of A only, and the products run every tile over the k-steps its triangle
  * leaves nonzero, (T + 1) / 2T of the full product's (T = tiles of 256 along A; "gemm_i8_trmm_kernel" /
  * "gemm_i8_trmm_onetile_kernel").  Padded k beyond 2^16 runs gemmul8_gemm's products over all tiles.
- * Real types only, in the combinations gemmul8_gemm accepts for type_a / type_b / type_c under
- * GEMMUL8_REAL_DEFAULT; a complex type returns GEMMUL8_E_TYPES; GEMMUL8_OP_C or an unknown side / uplo / diag
- * GEMMUL8_E_OP; moduli, size and leading-dimension checks are gemmul8_gemm's (lda >= m on the left, >= n on the
- * right; ldb, ldc >= m); m == 0 or n == 0 returns GEMMUL8_OK; on any error nothing is enqueued.  phase_ns as
- * gemmul8_gemm.  gemmul8_work_size_trmm(side, m, n, N) == gemmul8_work_size(m, n, side == LEFT ? m : n, N,
- * GEMMUL8_REAL_DEFAULT). */
+ * Types: all real, in the combinations gemmul8_gemm accepts for type_a / type_b / type_c under
+ * GEMMUL8_REAL_DEFAULT, or all complex (below); a mix of real and complex types returns GEMMUL8_E_TYPES;
+ * GEMMUL8_OP_C with real types or an unknown side / uplo / diag GEMMUL8_E_OP; moduli, size and leading-dimension
+ * checks are gemmul8_gemm's (lda >= m on the left, >= n on the right; ldb, ldc >= m); m == 0 or n == 0 returns
+ * GEMMUL8_OK; on any error nothing is enqueued.  phase_ns as gemmul8_gemm.  gemmul8_work_size_trmm(side, m, n, N) ==
+ * gemmul8_work_size(m, n, side == LEFT ? m : n, N, GEMMUL8_REAL_DEFAULT).
+ * Complex form (ztrmm / ctrmm): type_a, type_b, type_c all in {C_64F, C_32F}, in the combinations gemmul8_gemm
+ * accepts under a complex compute type; trans may also be GEMMUL8_OP_C (op(A) = A^H); alpha points to one complex
+ * value of C's precision.  Neither part of an unreferenced element of A is read, a unit diagonal counts as 1 + 0i.
+ * C carries the bits gemmul8_gemm writes for the dense form in fast mode under any complex compute type, in
+ * accurate mode under GEMMUL8_COMPLEX_KARATSUBA_MULT (whose bound carries no reference defect).  The products
+ * always run on the Karatsuba geometry: per modulus the three sub-products of the sub-blocks [re | im | re + im],
+ * each tile of each over the k-steps the triangle leaves nonzero ("gemm_i8_trmm_kara_kernel" /
+ * "gemm_i8_trmm_kara_onetile_kernel"), so a skipped k-step is skipped three times; padded k beyond 2^16 runs
+ * gemmul8_gemm's products over all tiles of the same layout.  The workspace is
+ * gemmul8_work_size_trmm_complex(side, m, n, N), the Karatsuba layout's size at every shape (==
+ * gemmul8_work_size(m, n, side == LEFT ? m : n, N, GEMMUL8_COMPLEX_KARATSUBA_MULT) wherever gemmul8_gemm takes that
+ * geometry). */
 enum { GEMMUL8_SIDE_LEFT = 0, GEMMUL8_SIDE_RIGHT = 1 };
 enum { GEMMUL8_DIAG_NON_UNIT = 0, GEMMUL8_DIAG_UNIT = 1 };
 size_t gemmul8_work_size_trmm(int side, size_t m, size_t n, unsigned num_moduli);
+size_t gemmul8_work_size_trmm_complex(int side, size_t m, size_t n, unsigned num_moduli);
 int gemmul8_trmm(void *stream, int side, int uplo, int trans, int diag, size_t m, size_t n, int type_a, int type_b,
                  int type_c, const void *alpha, const void *A, size_t lda, const void *B, size_t ldb, void *C,
                  size_t ldc, unsigned num_moduli, int fastmode, void *work, double *phase_ns);
@@ -293,7 +306,8 @@ int gemmul8_get_epilogue(void);
  * ("gemm_i8_persistent_pg_kernel", "gemm_i8_persistent_kernel", "gemm_i8_kernel", "gemm_i8_small_kernel",
  * "gemm_i8_kernel (k-chunked)", "gemm_i8_batched_kernel", "gemm_i8_batched_onetile_kernel", "gemm_i8_syrk_kernel",
  * "gemm_i8_syrk_onetile_kernel", "gemm_i8_herk_kernel", "gemm_i8_herk_onetile_kernel", "gemm_i8_trmm_kernel",
- * "gemm_i8_trmm_onetile_kernel", "gemm_i8_splitk_kernel" (gemmul8_gemm and its low-memory, strided-batched-fallback
+ * "gemm_i8_trmm_onetile_kernel", "gemm_i8_trmm_kara_kernel", "gemm_i8_trmm_kara_onetile_kernel" (complex
+ * gemmul8_trmm), "gemm_i8_splitk_kernel" (gemmul8_gemm and its low-memory, strided-batched-fallback
  * and timing forms only: few output tiles, long k) or "none"; a gemmul8_syrk, gemmul8_herk or gemmul8_trmm call outside its own
  * kernels' domain reports the gemm kernel that ran all tiles). */
 const char *gemmul8_last_products_kernel(void);

@@ -2123,19 +2123,27 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_herk_onetile_kernel(SyrkA
 // each XCD holds the same share of every length (balanced queues), the whole launch runs one band of all the moduli
 // before the next shorter one, and the ~32 units an XCD has in flight come from one or two moduli's eighths
 // (4 clipped panels x a few of the other operand's each).
+// Complex operands (SUB below; Karatsuba geometry): the three sub-blocks [re | im | re + im] of the triangular
+// operand's plane are triangular with the same triangle, so each of the sub-products P1 = Ar Br, P2 = Ai Bi,
+// P3 = (Ar + Ai)(Br + Bi) of a modulus has the tile's clip.  A unit is (plane y in [0, 3 N), tile), modulus y / 3,
+// sub-product y mod 3 (syrk_unit's decode); its panels start kbeg panels into the tile's panel row of sub-block
+// y mod 3 (strides subA / subB), its residue tile goes to sub-plane y mod 3 of residue plane y / 3.  The order is the
+// one above with planes for moduli: band > plane > eighth, so an XCD's units in flight still come from one or two
+// planes of one band -- at most two sub-blocks' clipped panels, and a skipped k-step is skipped three times.
 struct TrmmArgs {
-    GemmArgs g;       // mtiles, ntiles, nplanes = N
+    GemmArgs g;       // mtiles, ntiles, nplanes = N (SUB: 3 N, the Karatsuba sub-products counted)
     unsigned Tc, To;  // tiles along the clipped dimension and along the other one
     unsigned on_n;    // 1: the clipped tile index is tn, else tm
     unsigned hi;      // 1: k >= t, else k <= t
     unsigned kmin;    // least unit length in k-steps (<= K): shorter units are widened into the encoded zeros
 };
 struct TrmmUnit {
-    unsigned j, tm, tn, klen;  // modulus, tile, k-steps
-    uint32_t offA, offB;       // byte offsets of the unit's first panels in plane j of A and of B
+    unsigned j, sb, tm, tn, klen;  // modulus, Karatsuba sub-product (SUB; else 0), tile, k-steps
+    uint32_t offA, offB;           // byte offsets of the unit's first panels in plane j of A and of B
 };
-// band b (4 b <= clip rank < 4 b + h), position pos in [0, h To) within it, modulus j
-__device__ __forceinline__ TrmmUnit trmm_unit(const TrmmArgs &a, unsigned j, unsigned b, unsigned h, unsigned pos) {
+// band b (4 b <= clip rank < 4 b + h), position pos in [0, h To) within it, plane y (SUB: 3 j + s, else modulus j)
+template <bool SUB>
+__device__ __forceinline__ TrmmUnit trmm_unit(const TrmmArgs &a, unsigned y, unsigned b, unsigned h, unsigned pos) {
     TrmmUnit u;
     pos = __builtin_amdgcn_readfirstlane(pos);
     const unsigned o = pos / h, c = 4 * b + (pos - o * h);
@@ -2145,12 +2153,16 @@ __device__ __forceinline__ TrmmUnit trmm_unit(const TrmmArgs &a, unsigned j, uns
         if (a.hi) kbeg = K - a.kmin;
         else kend = a.kmin;
     }
-    u.j = __builtin_amdgcn_readfirstlane(j);
+    u.j = __builtin_amdgcn_readfirstlane(SUB ? y / 3 : y);
+    u.sb = SUB ? __builtin_amdgcn_readfirstlane(y - 3 * u.j) : 0;
     u.tm = __builtin_amdgcn_readfirstlane(a.on_n ? o : t);
     u.tn = __builtin_amdgcn_readfirstlane(a.on_n ? t : o);
     u.klen = __builtin_amdgcn_readfirstlane(kend - kbeg);
-    u.offA = __builtin_amdgcn_readfirstlane((uint32_t)(((size_t)u.tm * a.g.kstride + kbeg) * PANEL));
-    u.offB = __builtin_amdgcn_readfirstlane((uint32_t)(((size_t)u.tn * a.g.kstride + kbeg) * PANEL));
+    // (SUB: the offsets stay inside sub-block sb, whose tile rows are kstride panels long like a real plane's)
+    u.offA = __builtin_amdgcn_readfirstlane(
+        (uint32_t)((SUB ? u.sb * a.g.subA : 0) + ((size_t)u.tm * a.g.kstride + kbeg) * PANEL));
+    u.offB = __builtin_amdgcn_readfirstlane(
+        (uint32_t)((SUB ? u.sb * a.g.subB : 0) + ((size_t)u.tn * a.g.kstride + kbeg) * PANEL));
     return u;
 }
 // share x of 8 of n items: first item and count (the first n mod 8 shares hold one more)
@@ -2167,7 +2179,9 @@ __device__ __forceinline__ void share8(unsigned n, unsigned x, unsigned &base, u
 // after step 2, where the next unit is known: hence 6) to the NEXT unit's first panel (its kbeg is in offA / offB),
 // and the drain of the block's last unit counts the current unit's steps.  The three steps staged after the jump
 // are the next unit's prologue whatever its length (>= 6 > 3).
-__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kernel(TrmmArgs a) {
+// SUB: the same kernel over the 3 N sub-product planes of the Karatsuba geometry (gemm_i8_trmm_kara_kernel: plane y
+// is sub-product y mod 3 of modulus y / 3, whose constants it takes); one body, SUB = false folds to the real kernel.
+template <bool SUB> __device__ __forceinline__ void trmm_persistent(const TrmmArgs &a) {
     static_assert(OZ2_MFMA16, "per-group epilogue: 16x16x64 accumulator map");
     __shared__ __attribute__((aligned(1024))) int8_t smem[PLDS_BYTES + PARK_SPARE];
     const GemmArgs &g = a.g;
@@ -2190,10 +2204,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kernel(TrmmArgs a) {
     auto unit_at = [&](unsigned i) {
         if (i < nF) {
             const unsigned b = i / perF, r = i - b * perF, y = r / txF;
-            return trmm_unit(a, y, b, 4, baseF + (r - y * txF));
+            return trmm_unit<SUB>(a, y, b, 4, baseF + (r - y * txF));
         }
         const unsigned r = i - nF, y = r / txL;
-        return trmm_unit(a, y, nfull, hl, baseL + (r - y * txL));
+        return trmm_unit<SUB>(a, y, nfull, hl, baseL + (r - y * txL));
     };
     auto claim = [&]() { return __hip_atomic_fetch_add(g.queue + xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
     auto to_unit = [&](unsigned pos) { return pos + 2 * nblk < total ? pos + 2 * nblk : NO_TILE; };
@@ -2330,8 +2344,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kernel(TrmmArgs a) {
         }
         __builtin_amdgcn_s_waitcnt((15) | (7 << 4) | (0 << 8) | (3 << 14));  // lgkmcnt(0), vmcnt untouched
         barrier();
-        uint8_t *out = static_cast<uint8_t *>(g.out) + (size_t)ct.j * g.planeOut + (size_t)ct.tn * 256 * g.ldo +
-                       (size_t)ct.tm * 256 + wr * 128;
+        uint8_t *out = static_cast<uint8_t *>(g.out) + (size_t)ct.j * g.planeOut + (SUB ? ct.sb * g.subOut : 0) +
+                       (size_t)ct.tn * 256 * g.ldo + (size_t)ct.tm * 256 + wr * 128;
 #pragma unroll
         for (int it = 0; it < PARK_STORES; ++it) {
             const int chunk = gtid + 256 * it;
@@ -2351,12 +2365,15 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kernel(TrmmArgs a) {
     }
     if (wr == 0) barrier();  // group 0 passed one barrier fewer (group 1's initial one)
 }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kernel(TrmmArgs a) { trmm_persistent<false>(a); }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kara_kernel(TrmmArgs a) { trmm_persistent<true>(a); }
 
 // One-unit form (K < 6, or fewer than 3 units per CU): grid (Tc To, N), block x of modulus y computes the unit at
 // raster position wgid(x) of the long-first raster above (the gemm one-tile kernel's XCD remap: an XCD's blocks are
 // a contiguous share, dispatched in order) with the one-tile kernel's ring, ping-pong loop and epilogue over the
 // unit's own steps.
-__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_onetile_kernel(TrmmArgs a) {
+// SUB (gemm_i8_trmm_kara_onetile_kernel): grid (Tc To, 3 N), blockIdx.y = 3 j + s.
+template <bool SUB> __device__ __forceinline__ void trmm_onetile(const TrmmArgs &a) {
     __shared__ __attribute__((aligned(1024))) int8_t smem[LDS_BYTES];
     const GemmArgs &g = a.g;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2367,7 +2384,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_onetile_kernel(TrmmA
     share8(nwg, bid & 7, base, cnt);
     const unsigned wgid = __builtin_amdgcn_readfirstlane(base + (bid >> 3));
     const unsigned b = wgid / (4 * a.To), h = min(4u, a.Tc - 4 * b);  // every band before the last is full
-    const TrmmUnit u = trmm_unit(a, blockIdx.y, b, h, wgid - b * 4 * a.To);
+    const TrmmUnit u = trmm_unit<SUB>(a, blockIdx.y, b, h, wgid - b * 4 * a.To);
 
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int8_t *)smem;
     const uint32_t lds_wave = lds_base + wave * 1024;
@@ -2422,8 +2439,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_onetile_kernel(TrmmA
     }
     if (wr == 0) barrier();
     barrier();  // all waves done with the ring before the epilogue reuses it
-    epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, 0, true, u.j);
+    epilogue<0>(g, acc, smem, tid, lane, wr, wc, u.tm, u.tn, u.j, u.sb, true, u.j);
 }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_onetile_kernel(TrmmArgs a) { trmm_onetile<false>(a); }
+__global__ __launch_bounds__(NTHREADS, 1) void gemm_i8_trmm_kara_onetile_kernel(TrmmArgs a) { trmm_onetile<true>(a); }
 
 // Exhaustive check of the two residue epilogues against exact arithmetic, every input and every
 // modulus: path 0 = biased (x in [-2^30, 2^30], the accumulator starting at bias_i), path 1 = signed
@@ -2893,11 +2912,14 @@ bool gemm_i8_herk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
 
 bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned N, KClip clip, uint8_t *R,
                   const ModParams &MP, hipStream_t st, uint32_t *queue, bool queue_zeroed) {
-    const size_t P = L.mtiles * L.ntiles, units = P * N;
+    // sub: a Karatsuba layout, the units counted over its 3 N sub-product planes
+    const bool sub = L.nsub == 3;
+    const unsigned planes = sub ? 3 * N : N;
+    const size_t P = L.mtiles * L.ntiles, units = P * planes;
     const char *ff = getenv("GEMMUL8_FORCE_FLAT_DMA");
-    // buffer descriptors (planes < 4 GiB), the biased residue path, one sub-product, 32-bit unit counts
-    if (L.nsub != 1 || L.ksteps == 0 || L.k_pad > ((size_t)1 << 16) || L.planeA >= ((size_t)1 << 32) ||
-        L.planeB >= ((size_t)1 << 32) || (ff && atoi(ff)) || N == 0 || N > 65535 || units == 0 || units > 0x0fffffffu)
+    // buffer descriptors (planes < 4 GiB), the biased residue path, 32-bit unit counts
+    if ((L.nsub != 1 && !sub) || L.ksteps == 0 || L.k_pad > ((size_t)1 << 16) || L.planeA >= ((size_t)1 << 32) ||
+        L.planeB >= ((size_t)1 << 32) || (ff && atoi(ff)) || N == 0 || planes > 65535 || units == 0 || units > 0x0fffffffu)
         return false;
     TrmmArgs a{};
     GemmArgs &g = a.g;
@@ -2908,11 +2930,14 @@ bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
     g.ksteps = g.kstride = (unsigned)L.ksteps;
     g.mtiles = (unsigned)L.mtiles;
     g.ntiles = (unsigned)L.ntiles;
-    g.nplanes = N;
+    g.nplanes = planes;
     g.out = R;
     g.planeOut = L.planeR;
     g.ldo = L.ldr;
-    g.nsub = 1;
+    g.nsub = sub ? 3 : 1;
+    g.subA = sub ? L.subA : 0;
+    g.subB = sub ? L.subB : 0;
+    g.subOut = sub ? L.subR : 0;
     g.biased = 1;
     for (int i = 0; i < OZ2_MAX_MODULI; ++i) {
         g.p[i] = MP.p[i];
@@ -2942,12 +2967,13 @@ bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
         }();
         const unsigned grid = (unsigned)std::min<size_t>(units, std::min(ncu, grid_cap ? std::max(grid_cap, 8u) : ncu));
         a.kmin = 6;
-        g_last_residue_kernel.store(12, std::memory_order_relaxed);
-        launch(gemm_i8_trmm_kernel, dim3(grid), dim3(NTHREADS), st, a);
+        g_last_residue_kernel.store(sub ? 15 : 12, std::memory_order_relaxed);
+        launch(sub ? gemm_i8_trmm_kara_kernel : gemm_i8_trmm_kernel, dim3(grid), dim3(NTHREADS), st, a);
     } else {
         a.kmin = 1;
-        g_last_residue_kernel.store(13, std::memory_order_relaxed);
-        launch(gemm_i8_trmm_onetile_kernel, dim3((unsigned)P, N), dim3(NTHREADS), st, a);
+        g_last_residue_kernel.store(sub ? 16 : 13, std::memory_order_relaxed);
+        launch(sub ? gemm_i8_trmm_kara_onetile_kernel : gemm_i8_trmm_onetile_kernel, dim3((unsigned)P, planes),
+               dim3(NTHREADS), st, a);
     }
     return true;
 }

@@ -827,8 +827,12 @@ static int run_herk(Call &c, bool upper, double *phase_ns) {
 // single-operand launches; everything runs on the caller's stream, and every operand is split before the CRT
 // writes C, which is what allows C == B.  The products are the k-clipped units (gemm_i8_trmm), or outside their
 // domain every tile over all of k through gemm_i8 (the zeros are encoded); the CRT is gemm's with beta = 0.
+// Complex operands: the layout is always the Karatsuba one (as run_herk: the residues of Re and Im are the same bits
+// under either geometry), whose sub-blocks [re | im | re + im] of the triangular operand share its triangle, so the
+// three sub-products of a modulus are k-clipped like the real product; the accurate-mode bound product keeps its
+// big-matrix geometry (phase_bound) over the masked magnitudes; the CRT is gemm's Karatsuba one.
 static int run_trmm(Call &c, KClip clip, double *phase_ns) {
-    const Views v = views(c.work, c.m, c.n, c.k, c.N, false);
+    const Views v = views(c.work, c.m, c.n, c.k, c.N, c.cplx, 0, 1);
     const Layout &L = v.L;
     const bool capturing = is_capturing(c.st);
     if (phase_ns && capturing)
@@ -864,8 +868,8 @@ static int run_trmm(Call &c, KClip clip, double *phase_ns) {
     if (!launch_ok()) return fail();
     {
         timing::Phase crt(record, c.st, nullptr, rec.crt1);
-        crt_inverse(v.R, L, v.sftA, v.sftB, make_crt_params(c.N, c.ot == OutType::F32), c.ot, c.alpha, c.beta, c.C,
-                    c.ldc, c.st, 0);
+        crt_inverse(v.R, L, v.sftA, v.sftB, make_crt_params(c.N, c.ot == OutType::F32 || c.ot == OutType::C32), c.ot,
+                    c.alpha, c.beta, c.C, c.ldc, c.st, 0);
         crt.end();
     }
     if (!launch_ok()) return fail();
@@ -891,26 +895,35 @@ size_t gemmul8_work_size_trmm(int side, size_t m, size_t n, unsigned num_moduli)
     return oz2::make_layout(m, n, side == GEMMUL8_SIDE_LEFT ? m : n, num_moduli, false).total;
 }
 
+size_t gemmul8_work_size_trmm_complex(int side, size_t m, size_t n, unsigned num_moduli) {
+    return oz2::make_layout(m, n, side == GEMMUL8_SIDE_LEFT ? m : n, num_moduli, true, 0, 1).total;
+}
+
 int gemmul8_trmm(void *stream, int side, int uplo, int trans, int diag, size_t m, size_t n, int type_a, int type_b,
                  int type_c, const void *alpha, const void *A, size_t lda, const void *B, size_t ldb, void *C,
                  size_t ldc, unsigned num_moduli, int fastmode, void *work, double *phase_ns) {
     if (num_moduli < 2 || num_moduli > 20) return GEMMUL8_E_MODULI;
-    if (type_a < 0 || type_a > 3 || type_b < 0 || type_b > 3 || type_c < 0 || type_c > 3 || oz2::dt_cplx(type_a) ||
-        oz2::dt_cplx(type_b) || oz2::dt_cplx(type_c))
+    if (type_a < 0 || type_a > 3 || type_b < 0 || type_b > 3 || type_c < 0 || type_c > 3)
         return GEMMUL8_E_TYPES;
-    if ((trans != GEMMUL8_OP_N && trans != GEMMUL8_OP_T) || (side != GEMMUL8_SIDE_LEFT && side != GEMMUL8_SIDE_RIGHT) ||
+    // all real or all complex
+    const bool cp = oz2::dt_cplx(type_a);
+    if (oz2::dt_cplx(type_b) != cp || oz2::dt_cplx(type_c) != cp) return GEMMUL8_E_TYPES;
+    if ((trans != GEMMUL8_OP_N && trans != GEMMUL8_OP_T && !(cp && trans == GEMMUL8_OP_C)) ||
+        (side != GEMMUL8_SIDE_LEFT && side != GEMMUL8_SIDE_RIGHT) ||
         (uplo != GEMMUL8_FILL_LOWER && uplo != GEMMUL8_FILL_UPPER) ||
         (diag != GEMMUL8_DIAG_NON_UNIT && diag != GEMMUL8_DIAG_UNIT))
         return GEMMUL8_E_OP;
-    static const double zero_d = 0.0;
-    static const float zero_f = 0.0f;
-    const void *beta = type_c == GEMMUL8_R_64F ? static_cast<const void *>(&zero_d) : &zero_f;
+    // beta = 0 of C's type (complex: both parts; the real forms read the first)
+    static const double zero_d[2] = {0.0, 0.0};
+    static const float zero_f[2] = {0.0f, 0.0f};
+    const void *beta = oz2::dt_dbl(type_c) ? static_cast<const void *>(zero_d) : zero_f;
     const bool right = side == GEMMUL8_SIDE_RIGHT;
+    const int ctype = cp ? GEMMUL8_COMPLEX_KARATSUBA_MULT : GEMMUL8_REAL_DEFAULT;
     oz2::Call c{};
     const int rc = right ? oz2::prepare(stream, GEMMUL8_OP_N, trans, m, n, n, type_b, type_a, type_c, alpha, B, ldb, A,
-                                        lda, beta, C, ldc, num_moduli, fastmode, work, GEMMUL8_REAL_DEFAULT, c)
+                                        lda, beta, C, ldc, num_moduli, fastmode, work, ctype, c)
                          : oz2::prepare(stream, trans, GEMMUL8_OP_N, m, n, m, type_a, type_b, type_c, alpha, A, lda, B,
-                                        ldb, beta, C, ldc, num_moduli, fastmode, work, GEMMUL8_REAL_DEFAULT, c);
+                                        ldb, beta, C, ldc, num_moduli, fastmode, work, ctype, c);
     if (rc != GEMMUL8_OK) return rc;
     if (phase_ns)
         for (int i = 0; i < 4; ++i) phase_ns[i] = 0.0;
@@ -1299,6 +1312,8 @@ const char *gemmul8_last_products_kernel(void) {
     case 12: return "gemm_i8_trmm_kernel";
     case 13: return "gemm_i8_trmm_onetile_kernel";
     case 14: return "gemm_i8_splitk_kernel";
+    case 15: return "gemm_i8_trmm_kara_kernel";
+    case 16: return "gemm_i8_trmm_kara_onetile_kernel";
     default: return "none";
     }
 }

@@ -71,9 +71,10 @@ struct OperandDesc {
     bool dbl;      // real part is f64 (else f32)
     bool cplx;
     bool conj;     // op C of a complex operand
-    // triangular operand (gemmul8_trmm; real, single-operand launches only): element e of vector v is taken from
+    // triangular operand (gemmul8_trmm; single-operand launches only): element e of vector v is taken from
     // memory only inside the kept range -- TRI_LE: e <= v, TRI_GE: e >= v -- and is exactly 0 outside it, whatever
-    // the memory holds; unit: e == v is exactly 1 and not read either
+    // the memory holds; unit: e == v is exactly 1 and not read either (complex: both parts 0, resp. (1, 0); conj
+    // applies to the masked value)
     int tri = TRI_NONE;
     bool unit = false;
 };
@@ -181,7 +182,10 @@ bool gemm_i8_herk(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
 // gemm_i8_trmm_onetile_kernel): every tile of the N residue planes R, each over the k-steps its triangle leaves
 // nonzero.  With t the tile's index along the clipped dimension (on_n: tn, else tm) and K = L.ksteps:
 // hi = false ("k <= t") steps [0, min(K, 4 (t + 1))), hi = true ("k >= t") steps [4 t, K); queue as gemm_i8.
-// false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB, forced flat DMA, sub-products)
+// A Karatsuba layout (nsub = 3, complex trmm; gemm_i8_trmm_kara_kernel / gemm_i8_trmm_kara_onetile_kernel): the same
+// units over the 3 N sub-product planes, sub-product s of modulus j from sub-block s of A8's and of B8's plane j into
+// sub-plane s of R's plane j, all three with the tile's clip; the launch rule counts 3 N tiles units.
+// false (nothing launched) outside the kernels' domain (k_pad > 2^16, planes of 4 GiB, forced flat DMA)
 struct KClip {
     bool on_n, hi;
 };
@@ -191,7 +195,7 @@ bool gemm_i8_trmm(const int8_t *A8, const int8_t *B8, const Layout &L, unsigned 
 // 2 persistent (gemm_i8_persistent_kernel), 3 k-chunked one-tile launches, 4 128 x 128 (gemm_i8_small_kernel),
 // 5 persistent per-group (gemm_i8_persistent_pg_kernel), 6 / 7 batched persistent / one-unit, 8 / 9 SYRK
 // persistent / one-unit, 10 / 11 HERK persistent / one-unit, 12 / 13 TRMM persistent / one-unit, 14 split-K
-// (gemm_i8_splitk_kernel);
+// (gemm_i8_splitk_kernel), 15 / 16 Karatsuba TRMM persistent / one-unit;
 // g_last_tail_small: its last planes ran as 128 x 128 tiles
 extern std::atomic<int> g_last_residue_kernel;
 extern std::atomic<int> g_last_tail_small;

@@ -175,20 +175,21 @@ __device__ __forceinline__ void load_elem(const R *__restrict__ X, size_t idx, R
     }
 }
 
-// Triangular operand (OperandDesc::tri, gemmul8_trmm; real): element e of vector v is read only inside the kept
-// range (TRI_GE: e >= v, else e <= v); outside it is exactly 0 and with TRI_UNIT e == v is exactly 1, neither taken
-// from memory (which may hold anything, NaN included).  A zero leaves amax and the round-up sum of squares as they
-// are (s + 0 * 0 = s exactly), so the bodies below keep their loops and their order of operations.  TRI = false
-// folds to load_elem: the instantiations of the dense entry points keep their code.
+// Triangular operand (OperandDesc::tri, gemmul8_trmm): element e of vector v is read only inside the kept
+// range (TRI_GE: e >= v, else e <= v); outside it is exactly 0 and with TRI_UNIT e == v is exactly 1 (complex: both
+// parts 0, resp. (1, 0)), neither taken from memory (which may hold anything, NaN included).  A zero leaves amax and
+// the round-up sum of squares as they are (s + 0 * 0 = s exactly), so the bodies below keep their loops and their
+// order of operations.  The mask sits before the conjugation and the Karatsuba sum of the encode, so op C and the
+// three sub-blocks [re | im | re + im] see the masked value.  TRI = false folds to load_elem: the instantiations of
+// the dense entry points keep their code.
 template <typename R, bool CPLX, bool NT, bool TRI>
 __device__ __forceinline__ void load_op(const R *__restrict__ X, size_t idx, size_t e, size_t v, int tri, R &re, R &im) {
     if constexpr (TRI) {
-        static_assert(!CPLX, "triangular operands are real");
         const bool diag = (tri & TRI_UNIT) && e == v;
         const bool keep = (tri & TRI_GE) ? e >= v : e <= v;
         re = diag ? R(1) : R(0);
         im = 0;
-        if (keep && !diag) re = NT ? __builtin_nontemporal_load(X + idx) : X[idx];
+        if (keep && !diag) load_elem<R, CPLX, NT>(X, idx, re, im);
     } else {
         load_elem<R, CPLX, NT>(X, idx, re, im);
     }
@@ -313,14 +314,14 @@ __global__ __launch_bounds__(VT) void stats_contig_kernel(const R *__restrict__ 
     stats_contig_body<R, CPLX, VT, ACCU, NT>(X, ld, len, nvec, log2M, sft_out, blockIdx.x, threadIdx.x, grp, gmax);
 }
 // the same pass over a triangular operand (tri: TRI_LE / TRI_GE, | TRI_UNIT)
-template <typename R, int VT, bool ACCU>
+template <typename R, bool CPLX, int VT, bool ACCU>
 __global__ __launch_bounds__(VT) void stats_contig_tri_kernel(const R *__restrict__ X, size_t ld, size_t len,
                                                              size_t nvec, float log2M, int16_t *__restrict__ sft_out,
                                                              int tri) {
     __shared__ R grp[32];
     __shared__ R gmax[8];
-    stats_contig_body<R, false, VT, ACCU, false, true>(X, ld, len, nvec, log2M, sft_out, blockIdx.x, threadIdx.x, grp,
-                                                       gmax, tri);
+    stats_contig_body<R, CPLX, VT, ACCU, false, true>(X, ld, len, nvec, log2M, sft_out, blockIdx.x, threadIdx.x, grp,
+                                                      gmax, tri);
 }
 
 // ------------------------------------------------------------------
@@ -437,13 +438,13 @@ __global__ __launch_bounds__(256) void stats_strided_kernel(const R *__restrict_
     stats_strided_body<R, CPLX, VT, ACCU, ROWS, NT>(X, ld, len, nvec, log2M, sft_out, bx, sh);
 }
 // the same pass over a triangular operand (tri: TRI_LE / TRI_GE, | TRI_UNIT)
-template <typename R, int VT, bool ACCU, int ROWS>
+template <typename R, bool CPLX, int VT, bool ACCU, int ROWS>
 __global__ __launch_bounds__(256) void stats_strided_tri_kernel(const R *__restrict__ X, size_t ld, size_t len,
                                                                size_t nvec, float log2M,
                                                                int16_t *__restrict__ sft_out, int tri) {
     __shared__ StridedShared<R, VT, ROWS> sh;
     const unsigned bx = ROWS < 16 && OZ2_STATS_XCD ? xcd_local_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    stats_strided_body<R, false, VT, ACCU, ROWS, false, true>(X, ld, len, nvec, log2M, sft_out, bx, sh, tri);
+    stats_strided_body<R, CPLX, VT, ACCU, ROWS, false, true>(X, ld, len, nvec, log2M, sft_out, bx, sh, tri);
 }
 
 // Both operands' fast-mode shifts in one launch (small problems, one stream; real f64, A rows strided,
@@ -890,17 +891,18 @@ __global__ __launch_bounds__(CPLX ? 128 : 256) void encode_kernel(const R *__res
     encode_body<R, CPLX, CONTIG, IS_A, MODE, NTL>(X, ld, nvec, len, sft, out, plane, ksteps, kblk, vmax, flags, MP, G,
                                              blockIdx.x, blockIdx.y, tile);
 }
-// the same encode of a triangular operand (real; tri: TRI_LE / TRI_GE, | TRI_UNIT)
-template <typename R, bool CONTIG, int MODE>
-__global__ __launch_bounds__(256) void encode_tri_kernel(const R *__restrict__ X, size_t ld, size_t nvec, size_t len,
-                                                        const int16_t *__restrict__ sft, int8_t *__restrict__ out,
-                                                        size_t plane, size_t ksteps, size_t kblk, size_t vmax,
-                                                        int flags, ModParams MP, ModGroups G, int tri) {
-    __shared__ EncTile<R, false> tile;
+// the same encode of a triangular operand (tri: TRI_LE / TRI_GE, | TRI_UNIT)
+template <typename R, bool CPLX, bool CONTIG, bool IS_A, int MODE>
+__global__ __launch_bounds__(CPLX ? 128 : 256) void encode_tri_kernel(const R *__restrict__ X, size_t ld, size_t nvec,
+                                                                       size_t len, const int16_t *__restrict__ sft,
+                                                                       int8_t *__restrict__ out, size_t plane,
+                                                                       size_t ksteps, size_t kblk, size_t vmax,
+                                                                       int flags, ModParams MP, ModGroups G, int tri) {
+    __shared__ EncTile<R, CPLX> tile;
     if (MP.zero_queue && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8) MP.zero_queue[threadIdx.x] = 0;
-    encode_body<R, false, CONTIG, false, MODE, false, false, true>(X, ld, nvec, len, sft, out, plane, ksteps, kblk, vmax,
-                                                                   flags, MP, G, blockIdx.x, blockIdx.y, tile, nullptr,
-                                                                   tri);
+    encode_body<R, CPLX, CONTIG, IS_A, MODE, false, false, true>(X, ld, nvec, len, sft, out, plane, ksteps, kblk, vmax,
+                                                                 flags, MP, G, blockIdx.x, blockIdx.y, tile, nullptr,
+                                                                 tri);
 }
 
 // ------------------------------------------------------------------
@@ -1486,25 +1488,23 @@ template <typename R, bool CPLX>
 static void launch_stats(const void *X, size_t ld, bool contig, size_t len, size_t nvec, int VT, bool accurate,
                          float log2M, int16_t *out, hipStream_t st, int tri = 0) {
     const R *x = static_cast<const R *>(X);
-    if constexpr (!CPLX) {
-        if (tri) {  // triangular operand: the same grids, the kernels that honour the kept range (plain loads)
-            if (contig) {
-#define OZ2_SCT(vt, ac) launch(stats_contig_tri_kernel<R, vt, ac>, dim3((unsigned)nvec), dim3(vt), st, x, ld, len, nvec, log2M, out, tri)
-                if (VT == 512) { if (accurate) OZ2_SCT(512, true); else OZ2_SCT(512, false); }
-                else { if (accurate) OZ2_SCT(128, true); else OZ2_SCT(128, false); }
+    if (tri) {  // triangular operand: the same grids, the kernels that honour the kept range (plain loads)
+        if (contig) {
+#define OZ2_SCT(vt, ac) launch(stats_contig_tri_kernel<R, CPLX, vt, ac>, dim3((unsigned)nvec), dim3(vt), st, x, ld, len, nvec, log2M, out, tri)
+            if (VT == 512) { if (accurate) OZ2_SCT(512, true); else OZ2_SCT(512, false); }
+            else { if (accurate) OZ2_SCT(128, true); else OZ2_SCT(128, false); }
 #undef OZ2_SCT
-            } else {
-                const int rows = stats_rows(nvec);
-                const unsigned g = (unsigned)((nvec + rows - 1) / rows);
-#define OZ2_SST(vt, ac) do { if (rows == 16) launch(stats_strided_tri_kernel<R, vt, ac, 16>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); \
-                             else if (rows == 8) launch(stats_strided_tri_kernel<R, vt, ac, 8>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); \
-                             else launch(stats_strided_tri_kernel<R, vt, ac, 4>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); } while (0)
-                if (VT == 512) { if (accurate) OZ2_SST(512, true); else OZ2_SST(512, false); }
-                else { if (accurate) OZ2_SST(128, true); else OZ2_SST(128, false); }
+        } else {
+            const int rows = stats_rows(nvec);
+            const unsigned g = (unsigned)((nvec + rows - 1) / rows);
+#define OZ2_SST(vt, ac) do { if (rows == 16) launch(stats_strided_tri_kernel<R, CPLX, vt, ac, 16>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); \
+                             else if (rows == 8) launch(stats_strided_tri_kernel<R, CPLX, vt, ac, 8>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); \
+                             else launch(stats_strided_tri_kernel<R, CPLX, vt, ac, 4>, dim3(g), dim3(256), st, x, ld, len, nvec, log2M, out, tri); } while (0)
+            if (VT == 512) { if (accurate) OZ2_SST(512, true); else OZ2_SST(512, false); }
+            else { if (accurate) OZ2_SST(128, true); else OZ2_SST(128, false); }
 #undef OZ2_SST
-            }
-            return;
         }
+        return;
     }
     const bool nt = nvec * len * sizeof(R) * (CPLX ? 2 : 1) >= NT_OPERAND_BYTES;
     if (contig) {
@@ -1552,16 +1552,14 @@ static void launch_encode(const void *X, size_t ld, bool contig, size_t nvec, si
     if constexpr (std::is_same<R, float>::value) {
         if (mode == 0 && !G.f32_exact) mode = 2;
     }
-    if constexpr (!CPLX && !IS_A) {
-        if (tri) {  // triangular operand: the same grid, the kernels that honour the kept range (plain loads)
-#define OZ2_ENT(cg, md) launch(encode_tri_kernel<R, cg, md>, grid, dim3(NT), st, x, ld, nvec, len, sft, out, plane, L.ksteps, L.kblk, vmax, flags, MP, G, tri)
+    if (tri) {  // triangular operand: the same grid, the kernels that honour the kept range (plain loads)
+#define OZ2_ENT(cg, md) launch(encode_tri_kernel<R, CPLX, cg, IS_A, md>, grid, dim3(NT), st, x, ld, nvec, len, sft, out, plane, L.ksteps, L.kblk, vmax, flags, MP, G, tri)
 #define OZ2_ENT_F32(cg) do { if constexpr (std::is_same<R, float>::value) OZ2_ENT(cg, 2); } while (0)
-            if (contig) { if (mode == 0) OZ2_ENT(true, 0); else if (mode == 1) OZ2_ENT(true, 1); else OZ2_ENT_F32(true); }
-            else { if (mode == 0) OZ2_ENT(false, 0); else if (mode == 1) OZ2_ENT(false, 1); else OZ2_ENT_F32(false); }
+        if (contig) { if (mode == 0) OZ2_ENT(true, 0); else if (mode == 1) OZ2_ENT(true, 1); else OZ2_ENT_F32(true); }
+        else { if (mode == 0) OZ2_ENT(false, 0); else if (mode == 1) OZ2_ENT(false, 1); else OZ2_ENT_F32(false); }
 #undef OZ2_ENT_F32
 #undef OZ2_ENT
-            return;
-        }
+        return;
     }
     if (contig) { if (mode == 0) OZ2_EN(true, 0); else if (mode == 1) OZ2_EN(true, 1); else OZ2_EN_F32(true); }
     else { if (mode == 0) OZ2_EN(false, 0); else if (mode == 1) OZ2_EN(false, 1); else OZ2_EN_F32(false); }
@@ -1569,19 +1567,19 @@ static void launch_encode(const void *X, size_t ld, bool contig, size_t nvec, si
 #undef OZ2_EN
 }
 
-// the kernels' triangle argument of a (real) operand: 0, or TRI_LE / TRI_GE with the TRI_UNIT bit
+// the kernels' triangle argument of an operand: 0, or TRI_LE / TRI_GE with the TRI_UNIT bit
 static int tri_arg(const OperandDesc &d) {
-    return d.cplx || d.tri == TRI_NONE ? 0 : d.tri | (d.unit ? TRI_UNIT : 0);
+    return d.tri == TRI_NONE ? 0 : d.tri | (d.unit ? TRI_UNIT : 0);
 }
 
 void split_stats(const OperandDesc &d, size_t len, size_t nvec, int VT, bool accurate, float log2M, int16_t *out,
                  hipStream_t st) {
     const int tri = tri_arg(d);
     if (d.dbl) {
-        if (d.cplx) launch_stats<double, true>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st);
+        if (d.cplx) launch_stats<double, true>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st, tri);
         else launch_stats<double, false>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st, tri);
     } else {
-        if (d.cplx) launch_stats<float, true>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st);
+        if (d.cplx) launch_stats<float, true>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st, tri);
         else launch_stats<float, false>(d.ptr, d.ld, d.contig, len, nvec, VT, accurate, log2M, out, st, tri);
     }
 }

@@ -72,6 +72,8 @@ def _load():
     lib.gemmul8_herk.argtypes = [p, i, i, sz, sz, i, i, p, p, sz, p, p, sz, u, i, p, d]
     lib.gemmul8_work_size_trmm.restype = sz
     lib.gemmul8_work_size_trmm.argtypes = [i, sz, sz, u]
+    lib.gemmul8_work_size_trmm_complex.restype = sz
+    lib.gemmul8_work_size_trmm_complex.argtypes = [i, sz, sz, u]
     lib.gemmul8_trmm.restype = i
     lib.gemmul8_trmm.argtypes = [p, i, i, i, i, sz, sz, i, i, i, p, p, sz, p, sz, p, sz, u, i, p, d]
     lib.gemmul8_timing_enable.argtypes = [i]
@@ -227,18 +229,22 @@ def herk(uplo, trans, n, k, alpha, A, lda, beta, C, ldc, num_moduli, fastmode, w
     return list(pt) if phase_times else None
 
 
-def workSize_trmm(side, m, n, num_moduli):
-    """Bytes of device workspace for trmm: workSize(m, n, m if side == SIDE_LEFT else n, num_moduli)."""
+def workSize_trmm(side, m, n, num_moduli, dtype=None):
+    """Bytes of device workspace for trmm: workSize(m, n, m if side == SIDE_LEFT else n, num_moduli); with a complex
+    dtype the Karatsuba geometry of that complex problem, which complex trmm takes at every shape."""
+    if dtype in (torch.complex128, torch.complex64):
+        return int(lib.gemmul8_work_size_trmm_complex(side, m, n, num_moduli))
     return int(lib.gemmul8_work_size_trmm(side, m, n, num_moduli))
 
 
 def trmm(side, uplo, trans, diag, m, n, alpha, A, lda, B, ldb, C, ldc, num_moduli, fastmode, work, stream=None,
          phase_times=False):
-    """C = alpha*op(A)*B (SIDE_LEFT, A m x m) or alpha*B*op(A) (SIDE_RIGHT, A n x n) on column-major real device
-    buffers, A triangular: only its `uplo` triangle is read (DIAG_UNIT: not the diagonal either, which counts as 1),
-    the rest may hold anything.  B and C are m x n; C is not read and may be B itself (ldc == ldb, one dtype).  C has
-    the bits gemm writes with beta = 0 for A's explicit dense form.  work holds workSize_trmm bytes.  Returns the
-    phase times like gemm."""
+    """C = alpha*op(A)*B (SIDE_LEFT, A m x m) or alpha*B*op(A) (SIDE_RIGHT, A n x n) on column-major device buffers,
+    all real (trans OP_N / OP_T) or all complex (also OP_C: op(A) = A^H; alpha complex), A triangular: only its `uplo`
+    triangle is read (DIAG_UNIT: not the diagonal either, which counts as 1), the rest may hold anything.  B and C are
+    m x n; C is not read and may be B itself (ldc == ldb, one dtype).  C has the bits gemm writes with beta = 0 for
+    A's explicit dense form (complex, accurate mode: under COMPLEX_KARATSUBA_MULT).  work holds workSize_trmm bytes
+    (complex: workSize_trmm(..., dtype=A.dtype)).  Returns the phase times like gemm."""
     ta, tb, tc = _DTYPE[A.dtype], _DTYPE[B.dtype], _DTYPE[C.dtype]
     al = _scalar(alpha, C.dtype)
     pt = (ctypes.c_double * 4)() if phase_times else None
